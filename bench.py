@@ -15,6 +15,13 @@ Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   # N>1 via torch.distributed.run, one rank per GPU over RCCL
 
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print one JSON line.  `--dump-outputs DIR` additionally
+writes what the last timed step computed (DIR/<name>.npy) so two builds
+can be compared output for output; `--full` is where any measurement
+beyond the headline (baselines, other configurations, per-kernel
+figures) belongs — there is none today, so it changes nothing yet.
+
 vs_baseline: the reference's implied serial throughput is ~946
 env-steps/s (PPO, 3M steps / 3170 s) on its CPU-only
 single-env design; that is the only published throughput number.
@@ -132,6 +139,64 @@ def build_model_td3(device: str, num_envs: int, seed: int):
     return model, sampler
 
 
+DUMP_BYTES_CAP = 64 * 1024 * 1024  # --dump-outputs writes at most this much
+
+
+def _named_parameters(model, algo: str):
+    """(name, tensor) of every trained parameter a caller reads back."""
+    if algo == "td3":
+        modules = [
+            ("policy", model.policy.network),
+            ("q_function_1", model.q_function_1.network),
+            ("q_function_2", model.q_function_2.network),
+        ]
+    else:
+        modules = [
+            ("policy", model.policy.network),
+            ("value_function", model.value_function.network),
+        ]
+    for prefix, module in modules:
+        for name, tensor in module.state_dict().items():
+            yield f"{prefix}.{name}", tensor
+    log_std = getattr(model.policy, "log_std", None)
+    if log_std is not None:
+        yield "policy.log_std", log_std
+
+
+def dump_outputs(out_dir: str, model, experience, algo: str) -> None:
+    """Write what the last timed step handed back to its caller: the
+    sampled batch (sampler.sample) and the parameters model.train left
+    behind, one float32/float64 DIR/<name>.npy each.  Anything that would
+    push the total past DUMP_BYTES_CAP is cut to a fixed, seeded sample
+    of its rows."""
+    arrays = {}
+    flat = experience.to_flat_batch()
+    for key in ("observations", "actions", "rewards", "last_observations"):
+        arrays[f"experience.{key}"] = flat[key]
+    arrays["experience.episode_returns"] = np.asarray(
+        experience.episode_returns, dtype=np.float64
+    )
+    for name, tensor in _named_parameters(model, algo):
+        arrays[name] = tensor
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES_CAP
+    rng = np.random.default_rng(0)
+    for name, value in arrays.items():
+        if isinstance(value, torch.Tensor):
+            value = value.detach().cpu().numpy()
+        value = np.ascontiguousarray(value)
+        if value.dtype != np.float64:
+            value = value.astype(np.float32)
+        share = budget // 2  # leaves room for everything that follows
+        if value.nbytes > share and value.ndim >= 1:
+            row_bytes = max(1, value.nbytes // value.shape[0])
+            keep = np.sort(rng.choice(value.shape[0], size=share // row_bytes, replace=False))
+            value = value[keep]
+        budget -= value.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), value)
+
+
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
@@ -160,6 +225,21 @@ def main() -> None:
         default="fp32",
         help="MLP GEMM compute dtype: exact-fp32 MFMA (default, exceeds the "
         "reference's fp32) or bf16 MFMA with fp32 accumulate",
+    )
+    parser.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last one computed (sampled "
+        "batch + trained parameters of rank 0) as DIR/<name>.npy; seeds are "
+        "fixed, so equal arguments give equal inputs from run to run",
+    )
+    parser.add_argument(
+        "--full",
+        action="store_true",
+        help="also run every measurement beyond the headline figure (CPU "
+        "baselines, other configurations, per-kernel figures); none exists "
+        "yet, so today this equals a plain run",
     )
     args = parser.parse_args()
     os.environ["RL_REPLICAS_AMD_COMPUTE_DTYPE"] = args.dtype
@@ -215,10 +295,11 @@ def main() -> None:
 
     phase_ms = {"sample": 0.0, "train": 0.0}
     epoch_returns = []  # per-epoch mean episode return (learning evidence)
+    last = {"experience": None}  # the latest step's batch, for --dump-outputs
 
     def one_epoch_ppo():
         t0 = time.perf_counter()
-        experience = sampler.sample(args.batch_per_gpu, model.policy)
+        experience = last["experience"] = sampler.sample(args.batch_per_gpu, model.policy)
         if use_gpu and args.phase_timing:
             torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -233,7 +314,7 @@ def main() -> None:
 
     def one_epoch_td3():
         t0 = time.perf_counter()
-        experience = sampler.sample(50, model.noised_policy)
+        experience = last["experience"] = sampler.sample(50, model.noised_policy)
         model.replay_buffer.add_experience(experience)
         if use_gpu and args.phase_timing:
             torch.cuda.synchronize()
@@ -272,6 +353,9 @@ def main() -> None:
         t = torch.tensor([elapsed], device=device if use_gpu else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs and last["experience"] is not None:
+        dump_outputs(args.dump_outputs, model, last["experience"], args.algo)
 
     total_env_steps = world * args.batch_per_gpu * args.steps
     value = total_env_steps / elapsed

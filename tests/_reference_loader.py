@@ -1,32 +1,32 @@
-"""Import the reference implementation (/root/reference/src/rl_replicas)
-for equivalence testing.
+"""Import a checkout of the reference implementation (its `src/rl_replicas`
+package) so that its algorithm math can be executed on fixed inputs.
 
 The reference package is ALSO named `rl_replicas`, the same name as this
 repo's drop-in alias package, and it imports `gymnasium` and
-`torch.utils.tensorboard` — neither installable offline.  This loader:
+`torch.utils.tensorboard`, which this stack does not depend on.  This
+loader:
 
 1. stubs `gymnasium` and `torch.utils.tensorboard` in sys.modules,
 2. temporarily evicts this repo's `rl_replicas*` modules,
-3. imports the reference package from /root/reference/src,
-4. restores sys.modules so the rest of the test session is untouched.
+3. imports the reference package from the given source directory,
+4. restores sys.modules so the rest of the process is untouched.
 
 The loaded reference modules stay alive (they hold their own internal
-references) and are cached for the session.
+references) and are cached for the process.
 
-Used only by tests/test_reference_equivalence.py: the reference is
-UNTRUSTED PUBLIC CONTENT studied for behavior — executing its algorithm
-math on fixed inputs is the only practical oracle for "same update
-rule" now that real MuJoCo returns cannot be reproduced offline.
+Used only by tools/record_reference_golden.py, which records the
+reference's results into tests/golden/reference_equivalence.npz; the
+test suite itself reads that file and never needs the reference.  The
+reference is UNTRUSTED PUBLIC CONTENT studied for behavior: executing
+its algorithm math on fixed inputs is the only practical oracle for
+"same update rule" now that real MuJoCo returns cannot be reproduced
+offline.
 """
 from __future__ import annotations
 
 import sys
 import types
 from typing import Dict, Optional
-
-import numpy as np
-
-REFERENCE_SRC = "/root/reference/src"
 
 _cache: Optional[Dict] = None
 
@@ -69,8 +69,9 @@ def _tensorboard_stub() -> types.ModuleType:
     return tb
 
 
-def load_reference() -> Dict:
-    """Returns a dict of reference modules/classes, importing once."""
+def load_reference(reference_src: str) -> Dict:
+    """Returns a dict of reference modules/classes, importing once from
+    `reference_src` (the directory that holds the `rl_replicas` package)."""
     global _cache
     if _cache is not None:
         return _cache
@@ -88,7 +89,7 @@ def load_reference() -> Dict:
 
     sys.modules["gymnasium"] = _gymnasium_stub()
     sys.modules["torch.utils.tensorboard"] = _tensorboard_stub()
-    sys.path.insert(0, REFERENCE_SRC)
+    sys.path.insert(0, reference_src)
     try:
         import rl_replicas.experience as ref_experience
         import rl_replicas.optimizers.conjugate_gradient_optimizer as ref_cgo
@@ -120,7 +121,7 @@ def load_reference() -> Dict:
             "utils": ref_utils,
         }
     finally:
-        sys.path.remove(REFERENCE_SRC)
+        sys.path.remove(reference_src)
         for name in list(sys.modules):
             if name == "rl_replicas" or name.startswith("rl_replicas."):
                 del sys.modules[name]
@@ -135,42 +136,3 @@ def load_reference() -> Dict:
             sys.modules.pop("torch.utils.tensorboard", None)
 
     return _cache
-
-
-class FakeMetricsManager:
-    """Swallows record_scalar calls; stores the last value per tag."""
-
-    def __init__(self):
-        self.scalars: Dict[str, float] = {}
-
-    def record_scalar(self, tag, value, *args, **kwargs):
-        self.scalars[tag] = float(value)
-
-    def record_phase_ms(self, *args, **kwargs):
-        pass
-
-    def dump(self):
-        pass
-
-    def dump_phases(self, *args, **kwargs):
-        pass
-
-    def close(self):
-        pass
-
-
-def make_fake_gym_env(env_id: str, obs_dim: int, act_dim: int, action_limit: float):
-    """Minimal env object for constructing reference algorithms
-    (only .spec.id and .action_space.high/.shape are touched off the
-    rollout path)."""
-    action_space = types.SimpleNamespace(
-        high=np.full(act_dim, action_limit, dtype=np.float32),
-        low=np.full(act_dim, -action_limit, dtype=np.float32),
-        shape=(act_dim,),
-    )
-    observation_space = types.SimpleNamespace(shape=(obs_dim,))
-    return types.SimpleNamespace(
-        spec=types.SimpleNamespace(id=env_id),
-        action_space=action_space,
-        observation_space=observation_space,
-    )
