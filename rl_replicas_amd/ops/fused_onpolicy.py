@@ -317,10 +317,11 @@ class _GraphedPPO:
             self.loss0 = torch.zeros(1, device=dev)
             self.iters_done = torch.zeros(1, device=dev)
 
-            # mega path: ONE 3-kernel launch sequence per iteration
-            # (DO_FWD fused fwd+KL+loss+bwd, gate reduce, merged
-            # reduce+Adam incl. the log_std slot) — narrow fp32
-            # identity-head Gaussian policies (the bench config)
+            # mega path: ONE 2-kernel launch sequence per iteration
+            # (DO_FWD fused fwd+KL+loss+bwd, then merged reduce+Adam
+            # incl. the log_std slot with the gate bookkeeping folded
+            # in) — narrow fp32 identity-head Gaussian policies (the
+            # bench config)
             use_mega = False
             if kind == "gaussian" and ops.compute_bf16() == 0:
                 weights0, biases0, acts0 = _extract_layers(mlp)
@@ -553,7 +554,8 @@ class _GraphedValueLoop:
             # DO_FWD stages L extra activation tiles in LDS — mirror
             # the C++ budget gate so deep narrow nets fall back to the
             # separate-forward form instead of tripping the TORCH_CHECK
-            brows = 16 if obs0.shape[0] < 8192 else 32
+            # (backward tiles are 32 rows at every batch: bwd_fused_rows)
+            brows = 32
             whole_w = sum(
                 w.shape[0] * (w.shape[1] + 1) for w in _extract_layers(mlp)[0]
             )

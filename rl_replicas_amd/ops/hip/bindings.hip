@@ -27,14 +27,16 @@ void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
                           const float* mse_returns, float* loss_partials,
                           size_t lds_bytes, int n_blocks, int compute_bf16,
                           hipStream_t stream, int rows, int do_fwd = 0,
-                          GaussSeedArgs gargs = GaussSeedArgs{});
+                          GaussSeedArgs gargs = GaussSeedArgs{},
+                          int need_dx = 1);
 // Backward tiles stay at 32 rows: 16-row tiles made stage-1 faster but
 // DOUBLED the partial-row count, pushing the (latency-bound) reduce
 // from 10.3 to 17.8 us — a measured net loss.  (The FORWARD still uses
 // 16-row tiles below 8K rows; its cost has no reduce to pay.)
 inline int bwd_fused_rows(int batch) { (void)batch; return 32; }
 __global__ void mlp_grad_reduce_onepass_f32(ReduceAllArgs a);
-__global__ void mlp_grad_reduce_adam_f32(ReduceAdamArgs a);
+void launch_mlp_grad_reduce_adam(const ReduceAdamArgs& a, long grand,
+                                 hipStream_t stream);
 void launch_mlp_layer_fwd_wide(const float* x, const float* W, const float* B,
                                float* out, int batch, int in_d, int out_d,
                                int act, hipStream_t stream);
@@ -116,10 +118,6 @@ __global__ void fused_polyak_kernel(PolyakArgs a);
 __global__ void ppo_gate_update_kernel(float* gate, const float* kl,
                                        float* kl_final, float* iters_done,
                                        float thr);
-__global__ void ppo_gate_update_reduce_kernel(
-    float* gate, const float* kl_partials, const float* loss_partials,
-    int n_blocks, float inv_b, float* kl_final, float* iters_done, float thr,
-    float* loss_out, int first_iter);
 
 namespace {
 
@@ -176,9 +174,7 @@ void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
   ra.weight_decay = (float)weight_decay;
   ra.step_delta = (float)step_delta;
   ra.gate = gate.has_value() ? gate->data_ptr<float>() : nullptr;
-  int rb = (int)std::min<int64_t>(256, (grand + 63) / 64);
-  hipLaunchKernelGGL(mlp_grad_reduce_adam_f32, dim3(rb), dim3(256), 0, stream,
-                     ra);
+  launch_mlp_grad_reduce_adam(ra, (long)grand, stream);
   HIP_OK(hipGetLastError());
 }
 
@@ -715,11 +711,16 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
     dws[l] = torch::empty({(int)weights[l].size(0), (int)weights[l].size(1)}, opts);
     dbs[l] = torch::empty({(int)weights[l].size(0)}, opts);
   }
-  torch::Tensor dx = torch::empty({batch, x.size(1)}, opts);
-  launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr, dx.data_ptr<float>(),
+  // the fused-Adam mode consumes the gradient on device and nobody reads
+  // the input gradient: skip computing it and return an empty dx slot
+  torch::Tensor dx = fuse_adam ? torch::empty({0}, opts)
+                               : torch::empty({batch, x.size(1)}, opts);
+  launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr,
+                       fuse_adam ? nullptr : dx.data_ptr<float>(),
                        ws.data_ptr<float>(), returns.data_ptr<float>(),
                        loss_partials.data_ptr<float>(), fused_lds, fb,
-                       (int)compute_bf16, stream, brows, fwd_in_kernel ? 1 : 0);
+                       (int)compute_bf16, stream, brows, fwd_in_kernel ? 1 : 0,
+                       GaussSeedArgs{}, fuse_adam ? 0 : 1);
   HIP_OK(hipGetLastError());
 
   if (fuse_adam) {
@@ -1103,16 +1104,20 @@ void ppo_gate_update_(torch::Tensor gate, torch::Tensor kl,
   HIP_OK(hipGetLastError());
 }
 
-// ONE captured Gaussian-PPO policy iteration = 3 kernels:
+// ONE captured Gaussian-PPO policy iteration = 2 kernels:
 //   1. DO_FWD fused kernel: forward (LDS activations) + pending-KL /
 //      loss / dlog_std partials + clipped-surrogate dZ seed + whole-net
-//      backward stage-1
-//   2. gate reduce: close the gate if the pending KL crossed 1.5*maxkl
-//      (so this iteration's update is skipped, like the reference's
-//      break at ppo.py:176-181)
-//   3. merged reduce+Adam over net params AND log_std (pseudo-layer),
-//      gated
+//      backward stage-1 (no input gradient).  After the first iteration
+//      it returns at once while the gate is closed: a frozen iteration
+//      costs a launch, not a kernel.
+//   2. merged reduce+Adam over net params AND log_std (pseudo-layer)
+//      with the gate bookkeeping folded in: every workgroup sums the
+//      pending-KL partials and closes the gate if the KL crossed
+//      1.5*maxkl (so this iteration's update is skipped, like the
+//      reference's break at ppo.py:176-181); workgroup 0 records gate,
+//      kl_final, iters_done and the iteration-0 loss.
 // Narrow fp32 identity-head Gaussian policies only (the bench config).
+// The returned tensor is the (empty) dx slot.
 torch::Tensor gaussian_ppo_policy_iter(
     torch::Tensor x, std::vector<torch::Tensor> weights,
     std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
@@ -1155,7 +1160,6 @@ torch::Tensor gaussian_ppo_policy_iter(
   torch::Tensor ws = torch::empty({(int64_t)fb, grand_ls}, opts);
   torch::Tensor loss_partials = torch::empty({fb}, opts);
   torch::Tensor kl_partials = torch::empty({fb}, opts);
-  torch::Tensor dx = torch::empty({batch, x.size(1)}, opts);
 
   MLPBwdArgs ba{};
   ba.n_layers = L;
@@ -1178,23 +1182,22 @@ torch::Tensor gaussian_ppo_policy_iter(
   ga.kl_partials = kl_partials.data_ptr<float>();
   ga.dls_off = (int)grand;
   ga.clip = (float)clip;
+  // a frozen iteration skips the fused kernel.  The first iteration never
+  // gates and its loss partials are always read, so it always runs.
+  ga.skip_gate = first_iter ? nullptr : gate.data_ptr<float>();
 
-  launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr, dx.data_ptr<float>(),
+  // no input gradient: the update is fused, nobody reads dx
+  launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr, nullptr,
                        ws.data_ptr<float>(), nullptr,
                        loss_partials.data_ptr<float>(), fused_lds, fb, 0,
-                       stream, brows, 1, ga);
-  HIP_OK(hipGetLastError());
-
-  hipLaunchKernelGGL(ppo_gate_update_reduce_kernel, dim3(1), dim3(1), 0,
-                     stream, gate.data_ptr<float>(),
-                     kl_partials.data_ptr<float>(),
-                     loss_partials.data_ptr<float>(), fb, 1.f / (float)batch,
-                     kl_final.data_ptr<float>(), iters_done.data_ptr<float>(),
-                     (float)thr, loss_out.data_ptr<float>(),
-                     first_iter ? 1 : 0);
+                       stream, brows, 1, ga, 0);
   HIP_OK(hipGetLastError());
 
   TORCH_CHECK((int)adam_m.size() == 2 * L && (int)adam_v.size() == 2 * L);
+  for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
+    check_f32_gpu(*t, "gate/kl_final/iters_done/loss_out");
+    TORCH_CHECK(t->numel() == 1, "gate bookkeeping scalars must have 1 element");
+  }
   ReduceAdamArgs ra{};
   ra.ws = ws.data_ptr<float>();
   ra.stride = grand_ls;
@@ -1227,11 +1230,20 @@ torch::Tensor gaussian_ppo_policy_iter(
   ra.weight_decay = (float)weight_decay;
   ra.step_delta = (float)step_delta;
   ra.gate = gate.data_ptr<float>();
-  int rb = (int)std::min<int64_t>(256, (grand_ls + 63) / 64);
-  hipLaunchKernelGGL(mlp_grad_reduce_adam_f32, dim3(rb), dim3(256), 0, stream,
-                     ra);
+  // gate bookkeeping block: every workgroup derives the open/closed
+  // decision itself from the partials, workgroup 0 records it
+  ra.kl_partials = kl_partials.data_ptr<float>();
+  ra.loss_partials = loss_partials.data_ptr<float>();
+  ra.gate_rw = gate.data_ptr<float>();
+  ra.kl_final = kl_final.data_ptr<float>();
+  ra.iters_done = iters_done.data_ptr<float>();
+  ra.loss_out = loss_out.data_ptr<float>();
+  ra.inv_b = 1.f / (float)batch;
+  ra.thr = (float)thr;
+  ra.first_iter = first_iter ? 1 : 0;
+  launch_mlp_grad_reduce_adam(ra, (long)grand_ls, stream);
   HIP_OK(hipGetLastError());
-  return dx;
+  return torch::empty({0}, opts);  // dx slot: never computed here
 }
 
 void counter_add_(torch::Tensor ctr, int64_t delta) {
@@ -1280,7 +1292,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ppo_gate_update_", &ppo_gate_update_,
         "device-side KL early-stop gate bookkeeping (gfx950)");
   m.def("gaussian_ppo_policy_iter", &gaussian_ppo_policy_iter,
-        "one 3-kernel Gaussian-PPO policy iteration (gfx950)");
+        "one 2-kernel Gaussian-PPO policy iteration (gfx950)");
   m.def("segmented_gae", &segmented_gae, "segmented GAE+returns scan (gfx950)");
   m.def("normalize", &normalize, "fused mean/std normalize (gfx950)");
   m.def("q_target", &q_target, "fused Q-learning target (gfx950)");

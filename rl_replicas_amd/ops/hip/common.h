@@ -158,6 +158,18 @@ struct ReduceAdamArgs {
   int n_layers, n_blocks;
   float lr, beta1, beta2, eps, weight_decay, step_delta;
   const float* gate;  // optional: skip entirely while *gate == 0
+  // optional PPO gate bookkeeping (kl_partials != nullptr; needs gate):
+  // the kernel sums the fused iteration kernel's per-block pending-KL /
+  // loss partials itself, applies the KL early-stop rule and gates its
+  // own Adam update on the result (reduce_adam_gate_closed, mlp_kernels.hip)
+  const float* kl_partials;    // [n_blocks]
+  const float* loss_partials;  // [n_blocks]
+  float* gate_rw;              // == gate, writable (workgroup 0 only)
+  float* kl_final;
+  float* iters_done;
+  float* loss_out;
+  float inv_b, thr;
+  int first_iter;
 };
 
 // Gaussian-PPO seed for the DO_FWD fused backward (mlp_kernels.hip):
@@ -174,6 +186,9 @@ struct GaussSeedArgs {
   float* kl_partials;     // [n_blocks]
   int dls_off;            // flat ws offset of the dlog_std pseudo-layer
   float clip;
+  // optional: the whole kernel returns at once while *skip_gate == 0 (a
+  // gate-frozen policy iteration; its partials are never read then)
+  const float* skip_gate;
 };
 
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)

@@ -25,6 +25,8 @@
 // reduction (split-K via workspace instead of atomics so every run is
 // bitwise reproducible — SURVEY.md §4).  Workspace layout is
 // [block][all-layer elems] so the first reduction stage is layer-blind.
+#include <algorithm>
+
 #include "common.h"
 
 // ---------------------------------------------------------------------------
@@ -340,7 +342,10 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
 // path): x is staged once, every layer's activations land in LDS
 // (hlds) and never touch HBM; the MSE seed and the backward read them
 // from LDS.  fp32 only; requires mse_returns.
-template <int ROWS, bool BF16 = false, bool DO_FWD = false>
+// NEED_DX = false drops the layer-0 dgrad MFMA loop and the dx_out store
+// (batch x in_dim floats): the fused-Adam callers never read the input
+// gradient, so dx_out may be nullptr there.
+template <int ROWS, bool BF16 = false, bool DO_FWD = false, bool NEED_DX = true>
 __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
     MLPBwdArgs args, const float* __restrict__ x, const float* __restrict__ dy,
     float* __restrict__ dx_out, float* __restrict__ workspace,
@@ -350,6 +355,11 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
   constexpr int LDSW = MAXW + 4;
   constexpr int RT = ROWS / 16;
   constexpr int JT_STRIDE = 4 / RT;
+  // gate-frozen PPO iteration: a no-op by definition.  The only reader of
+  // this kernel's partials (the gated reduce+Adam kernel that follows)
+  // tests the same gate before it touches them, and nothing between the
+  // two launches reopens it.
+  if (DO_FWD && gargs.skip_gate != nullptr && *gargs.skip_gate == 0.f) return;
   extern __shared__ float smem[];
   float* const dza = smem;
   float* const dzb = smem + ROWS * LDSW;
@@ -554,11 +564,18 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
     }
 
     // ---- wgrad partials: dW[i][j] = sum_r dZ[r][i] X[r][j] ----
+    // The (it, jt) output tiles are independent, so the flattened tile
+    // list is dealt over the four waves (striding `it` alone left layers
+    // with out_d <= 32 on one or two waves).  Each tile's MFMA chain is
+    // unchanged.
     const int n_it = (out_d + 15) / 16;
+    const int n_jt = (in_d + 15) / 16;
     float* lw = wsp + (long)args.layer_off[l] * WSN;
-    for (int it = wave; it < n_it; it += 4) {
+    for (int t = wave; t < n_it * n_jt; t += 4) {
+      const int it = t / n_jt;
       const int ii = it * 16 + i;
-      for (int jt = 0; jt < in_d; jt += 16) {
+      {
+        const int jt = (t - it * n_jt) * 16;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         if constexpr (BF16) {
           for (int k0 = 0; k0 < ROWS; k0 += 32) {
@@ -588,8 +605,10 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
         }
       }
     }
-    // bias partial
-    for (int c = tid; c < out_d; c += 256) {
+    // bias partial: column c goes to thread 255 - c, i.e. to the last
+    // wave, which holds the fewest wgrad tiles whenever the tile count is
+    // no multiple of 4 (same serial row order per column)
+    for (int c = 255 - tid; c < out_d; c += 256) {
       float s = 0.f;
       #pragma unroll 4
       for (int r = 0; r < ROWS; ++r) s += dz_cur[r * LDSW + c];
@@ -598,6 +617,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
 
     // ---- dgrad: dX[b][j] = sum_k dZ[b][k] W[k][j]; for l>0 the next
     // activation-grad is fused from the staged X tile ----
+    if (!NEED_DX && l == 0) break;  // nobody reads the input gradient
     const int prev_act = l > 0 ? args.acts[l - 1] : ACT_IDENTITY;
     for (int jt = jt0; jt < in_d; jt += 16 * JT_STRIDE) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -881,42 +901,46 @@ __global__ __launch_bounds__(256) void mlp_bwd_wide_both_f32(
 
 // host-side dispatch over the (ROWS, MAXW) instantiations — called from
 // bindings.hip so template symbols stay in this translation unit
+template <int ROWS, bool BF16, bool DO_FWD>
+static void launch_mlp_bwd_fused_t(bool need_dx, const MLPBwdArgs& args,
+                                   const float* x, const float* dy, float* dx,
+                                   float* ws, const float* mse_returns,
+                                   float* loss_partials, size_t lds_bytes,
+                                   int n_blocks, hipStream_t stream,
+                                   const GaussSeedArgs& gargs) {
+  if (need_dx)
+    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<ROWS, BF16, DO_FWD, true>),
+                       dim3(n_blocks), dim3(256), lds_bytes, stream, args, x,
+                       dy, dx, ws, mse_returns, loss_partials, gargs);
+  else
+    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<ROWS, BF16, DO_FWD, false>),
+                       dim3(n_blocks), dim3(256), lds_bytes, stream, args, x,
+                       dy, dx, ws, mse_returns, loss_partials, gargs);
+}
+
+// need_dx == 0: dx may be nullptr (the kernel neither computes nor stores
+// the input gradient)
 void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
                           const float* dy, float* dx, float* ws,
                           const float* mse_returns, float* loss_partials,
                           size_t lds_bytes, int n_blocks, int compute_bf16,
                           hipStream_t stream, int rows, int do_fwd,
-                          GaussSeedArgs gargs) {
+                          GaussSeedArgs gargs, int need_dx) {
+  const bool ndx = need_dx != 0;
+#define BWD_FUSED_ARGS \
+  ndx, args, x, dy, dx, ws, mse_returns, loss_partials, lds_bytes, n_blocks, \
+      stream, gargs
   if (do_fwd) {  // fp32 only (host gates)
-    if (rows == 16)
-      hipLaunchKernelGGL((mlp_bwd_fused_f32_t<16, false, true>), dim3(n_blocks),
-                         dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                         mse_returns, loss_partials, gargs);
-    else
-      hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, false, true>), dim3(n_blocks),
-                         dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                         mse_returns, loss_partials, gargs);
-    return;
+    if (rows == 16) launch_mlp_bwd_fused_t<16, false, true>(BWD_FUSED_ARGS);
+    else launch_mlp_bwd_fused_t<32, false, true>(BWD_FUSED_ARGS);
+  } else if (rows == 16) {
+    if (compute_bf16) launch_mlp_bwd_fused_t<16, true, false>(BWD_FUSED_ARGS);
+    else launch_mlp_bwd_fused_t<16, false, false>(BWD_FUSED_ARGS);
+  } else {
+    if (compute_bf16) launch_mlp_bwd_fused_t<32, true, false>(BWD_FUSED_ARGS);
+    else launch_mlp_bwd_fused_t<32, false, false>(BWD_FUSED_ARGS);
   }
-  if (rows == 16) {
-    if (compute_bf16)
-      hipLaunchKernelGGL((mlp_bwd_fused_f32_t<16, true>), dim3(n_blocks),
-                         dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                         mse_returns, loss_partials);
-    else
-      hipLaunchKernelGGL((mlp_bwd_fused_f32_t<16, false>), dim3(n_blocks),
-                         dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                         mse_returns, loss_partials);
-    return;
-  }
-  if (compute_bf16)
-    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, true>), dim3(n_blocks),
-                       dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                       mse_returns, loss_partials);
-  else
-    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, false>), dim3(n_blocks),
-                       dim3(256), lds_bytes, stream, args, x, dy, dx, ws,
-                       mse_returns, loss_partials);
+#undef BWD_FUSED_ARGS
 }
 
 void launch_mlp_layer_fwd_wide(const float* x, const float* W, const float* B,
@@ -1000,9 +1024,70 @@ void launch_mlp_bwd_layer(const float* dy, const float* y, const float* xin,
 // reduce + Adam in one pass: identical fixed-order partial summation to
 // mlp_grad_reduce_onepass_f32, but the summed gradient feeds the Adam
 // update (same math as fused_adam_kernel) directly — no dw/db tensors.
+// ---------------------------------------------------------------------------
+
+// Gate prologue of the reduce+Adam kernels; returns true when this
+// workgroup must leave its Adam slice untouched.  Without kl_partials it
+// is the plain "skip while *gate == 0" test.  With them (the mega PPO
+// policy iteration) EVERY workgroup redoes the one-thread bookkeeping of
+// the former gate-reduce kernel — the per-block partials are staged
+// through LDS and thread 0 adds them in block order, the same serial
+// order as before — and gates its own slice on the result, so no kernel
+// boundary is needed between the decision and the update.  Only
+// workgroup 0 writes gate / kl_final / iters_done / loss_out.
+//
+// Workgroups of one launch may read the gate before or after workgroup 0
+// closes it.  Both views lead to the same decision: workgroup 0 closes
+// the gate only when kl > thr, and kl is a pure function of kl_partials
+// (final before this launch starts), summed in the same order by every
+// workgroup.  One that still sees the gate open therefore computes the
+// same kl, finds kl > thr and skips its slice; one that already sees it
+// closed skips its slice too.  Workgroup 0's own threads read the gate
+// before the first barrier below and thread 0 writes it after that
+// barrier, so its bookkeeping always acts on the value at entry.
+DEV_INLINE bool reduce_adam_gate_closed(const ReduceAdamArgs& a, float* stage) {
+  const float g_in = a.gate ? *a.gate : 1.f;
+  if (a.kl_partials == nullptr) return g_in == 0.f;
+  const int tid = threadIdx.x;
+  // closed on entry: nothing changes (the partials are stale then — the
+  // fused iteration kernel returned at once).  The first iteration never
+  // gates and always records its loss.
+  if (!a.first_iter && g_in == 0.f) return true;
+  if (a.first_iter && blockIdx.x != 0) return g_in == 0.f;
+  const float* part = a.first_iter ? a.loss_partials : a.kl_partials;
+  float acc = 0.f;  // thread 0's running sum
+  for (int base = 0; base < a.n_blocks; base += 256) {
+    const int cnt = min(256, a.n_blocks - base);
+    if (tid < cnt) stage[tid] = part[base + tid];
+    __syncthreads();
+    if (tid == 0) {
+      for (int j = 0; j < cnt; ++j) acc += stage[j];
+    }
+    __syncthreads();
+  }
+  if (a.first_iter) {
+    if (tid == 0) *a.loss_out = acc;  // no pending KL at iteration 0
+    return g_in == 0.f;
+  }
+  if (tid == 0) {
+    const float kl = acc * a.inv_b;
+    const bool close = kl > a.thr;
+    if (blockIdx.x == 0) {
+      *a.kl_final = kl;
+      *a.iters_done += 1.f;
+      if (close) *a.gate_rw = 0.f;
+    }
+    stage[0] = close ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const bool closed = stage[0] != 0.f;
+  __syncthreads();  // the caller reuses stage
+  return closed;
+}
+
 __global__ __launch_bounds__(256) void mlp_grad_reduce_adam_f32(ReduceAdamArgs a) {
-  if (a.gate && *a.gate == 0.f) return;
   __shared__ float red[256];
+  if (reduce_adam_gate_closed(a, red)) return;
   int grand = 0;
   int base[MLP_MAX_LAYERS];
   for (int l = 0; l < a.n_layers; ++l) {
@@ -1047,6 +1132,113 @@ __global__ __launch_bounds__(256) void mlp_grad_reduce_adam_f32(ReduceAdamArgs a
     }
     __syncthreads();
   }
+}
+
+// LDS-staged reduce+Adam for small partial counts.  In the element-major
+// workspace the partial rows of EPB consecutive elements are ONE
+// contiguous run of EPB * n_blocks floats, so the workgroup copies that
+// run into LDS with coalesced 16-byte loads (the direct kernel above has
+// every lane walk its own row, 4 bytes at a time, n_blocks * 4 bytes away
+// from its neighbour's) and sums from LDS.  EPB = 16 instead of 64
+// elements per workgroup quadruples the grid (205 workgroups for the
+// bench nets' 3265 elements instead of 52).  The arithmetic is the direct
+// kernel's: four quarter sums, each sequential from 0.f over
+// ceil(n_blocks/4) partials, combined as (q0+q1)+(q2+q3), then the same
+// Adam expression; the old p/m/v values are fetched before the copy so
+// their latency overlaps it.  Host side: dynamic LDS = EPB * n_blocks
+// floats, grid = ceil(grand / EPB).
+#define REDUCE_EPB 16
+#define REDUCE_STAGED_MAX_LDS (48 * 1024)  // bytes: n_blocks <= 768 at EPB 16
+#define REDUCE_STAGED_MAX_ELEMS 32768      // small nets only (grid = elems / 16)
+__global__ __launch_bounds__(256) void mlp_grad_reduce_adam_staged_f32(ReduceAdamArgs a) {
+  constexpr int EPB = REDUCE_EPB;
+  extern __shared__ __align__(16) float part[];  // [EPB][n_blocks], as in ws
+  __shared__ float red[256];
+  if (reduce_adam_gate_closed(a, red)) return;
+  int grand = 0;
+  int base[MLP_MAX_LAYERS];
+  for (int l = 0; l < a.n_layers; ++l) {
+    base[l] = grand;
+    grand += a.total[l];
+  }
+  const float s0 = a.step[0] + 1.f + a.step_delta;
+  const float bc1 = 1.f - __powf(a.beta1, s0);
+  const float bc2 = 1.f - __powf(a.beta2, s0);
+  const int tid = threadIdx.x;
+  const int nb = a.n_blocks;
+  const int g0 = blockIdx.x * EPB;
+  const int ne = min(EPB, grand - g0);  // elements of this workgroup (>= 1)
+
+  // this thread's Adam slot (threads 0..ne-1): old values fetched early
+  const int g = g0 + tid;
+  float *p = nullptr, *m = nullptr, *v = nullptr;
+  int idx = 0;
+  float p_old = 0.f, m_old = 0.f, v_old = 0.f;
+  if (tid < ne) {
+    int l = 0;
+    while (l + 1 < a.n_layers && g >= base[l + 1]) ++l;
+    idx = g - base[l];
+    if (idx < a.wsize[l]) {
+      p = a.pw[l]; m = a.mw[l]; v = a.vw[l];
+    } else {
+      idx -= a.wsize[l];
+      p = a.pb[l]; m = a.mb[l]; v = a.vb[l];
+    }
+    p_old = p[idx];
+    m_old = m[idx];
+    v_old = v[idx];
+  }
+
+  // coalesced copy of the run ws[g0 * nb, (g0 + ne) * nb): g0 is a
+  // multiple of EPB = 16, so the run starts 16-byte aligned
+  const int cnt = ne * nb;
+  const float* src = a.ws + (long)g0 * nb;
+  const int cnt4 = cnt >> 2;
+  const float4* src4 = reinterpret_cast<const float4*>(src);
+  float4* part4 = reinterpret_cast<float4*>(part);
+  for (int i = tid; i < cnt4; i += 256) part4[i] = src4[i];
+  for (int i = (cnt4 << 2) + tid; i < cnt; i += 256) part[i] = src[i];
+  __syncthreads();
+
+  const int e_local = tid % EPB;
+  const int quarter = tid / EPB;
+  if (quarter < 4) {
+    const int chunk = (nb + 3) / 4;
+    const int p0 = quarter * chunk;
+    const int p1 = min(p0 + chunk, nb);
+    float s = 0.f;
+    if (e_local < ne) {
+      for (int q = p0; q < p1; ++q) s += part[e_local * nb + q];
+    }
+    red[tid] = s;
+  }
+  __syncthreads();
+  if (tid < ne) {
+    float grad = (red[tid] + red[EPB + tid]) +
+                 (red[2 * EPB + tid] + red[3 * EPB + tid]);
+    if (a.weight_decay != 0.f) grad += a.weight_decay * p_old;
+    const float mi = a.beta1 * m_old + (1.f - a.beta1) * grad;
+    const float vi = a.beta2 * v_old + (1.f - a.beta2) * grad * grad;
+    m[idx] = mi;
+    v[idx] = vi;
+    p[idx] = p_old - a.lr * (mi / bc1) / (sqrtf(vi / bc2) + a.eps);
+  }
+}
+
+void launch_mlp_grad_reduce_adam(const ReduceAdamArgs& a, long grand,
+                                 hipStream_t stream) {
+  // staged: the partial rows of one workgroup fit a modest LDS slice and
+  // the net is small (large nets keep the grid-strided direct kernel)
+  const size_t staged_lds = (size_t)REDUCE_EPB * a.n_blocks * sizeof(float);
+  if (staged_lds <= REDUCE_STAGED_MAX_LDS && grand <= REDUCE_STAGED_MAX_ELEMS) {
+    const int rb = (int)((grand + REDUCE_EPB - 1) / REDUCE_EPB);
+    hipLaunchKernelGGL(mlp_grad_reduce_adam_staged_f32, dim3(rb), dim3(256),
+                       staged_lds, stream, a);
+    return;
+  }
+  const int rb = (int)std::min<long>(256, (grand + 63) / 64);
+  hipLaunchKernelGGL(mlp_grad_reduce_adam_f32, dim3(rb), dim3(256), 0, stream,
+                     a);
 }
 
 __global__ __launch_bounds__(256) void mlp_grad_reduce_onepass_f32(ReduceAllArgs a) {
