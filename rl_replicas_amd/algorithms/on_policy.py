@@ -191,17 +191,14 @@ class OnPolicyAlgorithm(AlgorithmBase):
         advantages = batch["advantages"]
         returns = batch["discounted_returns"]
 
-        policy_metrics = self._update_policy(obs, actions, advantages)
-
-        from rl_replicas_amd.ops import fused_onpolicy
-
-        if fused_onpolicy.value_supported(self, obs):
-            value_loss = fused_onpolicy.value_update(self, obs, returns, self.num_value_gradients)
+        # the two updates are independent (advantages and returns come from
+        # the pre-update value net), so an algorithm may run them jointly
+        joint = self._update_policy_and_value(obs, actions, advantages, returns)
+        if joint is not None:
+            policy_metrics, value_loss = joint
         else:
-            value_losses: List[float] = []
-            for _ in range(self.num_value_gradients):
-                value_losses.append(self.train_value_function(obs, returns).item())
-            value_loss = float(np.mean(value_losses))
+            policy_metrics = self._update_policy(obs, actions, advantages)
+            value_loss = self._update_value_function(obs, returns)
 
         m = self.metrics_manager
         for tag, value in policy_metrics.items():
@@ -217,6 +214,23 @@ class OnPolicyAlgorithm(AlgorithmBase):
     def _update_policy(self, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[str, float]:
         """Algorithm-specific policy update; returns metric tag->value."""
         raise NotImplementedError
+
+    def _update_policy_and_value(self, obs: Tensor, actions: Tensor, advantages: Tensor,
+                                 returns: Tensor):
+        """Optional joint policy + value update: (policy metrics, mean
+        value loss), or None to run the two updates one after the other."""
+        return None
+
+    def _update_value_function(self, obs: Tensor, returns: Tensor) -> float:
+        """num_value_gradients value-function steps; returns the mean loss."""
+        from rl_replicas_amd.ops import fused_onpolicy
+
+        if fused_onpolicy.value_supported(self, obs):
+            return fused_onpolicy.value_update(self, obs, returns, self.num_value_gradients)
+        value_losses: List[float] = []
+        for _ in range(self.num_value_gradients):
+            value_losses.append(self.train_value_function(obs, returns).item())
+        return float(np.mean(value_losses))
 
     def _policy_diagnostics(self, obs: Tensor, actions: Tensor) -> Dict[str, float]:
         """entropy / log_prob_std diagnostics (reference logs these

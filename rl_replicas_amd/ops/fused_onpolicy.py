@@ -199,6 +199,30 @@ def _ensure_adam_state(optimizer) -> List[Tensor]:
     return tensors
 
 
+def _fwd_in_kernel_fits(weights) -> bool:
+    """LDS budget of the fused kernels that run the forward themselves
+    (3 + L activation tiles of 32 rows + the padded weight image) —
+    mirrors the C++ gate (backward tiles are 32 rows at every batch:
+    bwd_fused_rows)."""
+    whole_w = sum(w.shape[0] * (w.shape[1] + 1) for w in weights)
+    return ((3 + len(weights)) * 32 * 68 + whole_w) * 4 <= 100 * 1024
+
+
+def _mega_eligible(policy, kind: str, obs: Tensor) -> bool:
+    """The 2-kernel policy iteration (gaussian_ppo_policy_iter): narrow
+    fp32 identity-head Gaussian policies (the bench config)."""
+    if kind != "gaussian" or ops.compute_bf16() != 0:
+        return False
+    weights, _, acts = _extract_layers(_mlp_of(policy))
+    return (
+        acts[-1] == 0  # identity head
+        and len(weights) + 1 <= 5
+        and policy.log_std.numel() <= 64
+        and max([obs.shape[1]] + [w.shape[0] for w in weights]) <= 64
+        and _fwd_in_kernel_fits(weights)
+    )
+
+
 class _CapturedLoop:
     """Capture `body()` into a hipGraph with state snapshot/restore
     around the warmup runs (warmup executes real kernels; capture does
@@ -322,19 +346,7 @@ class _GraphedPPO:
             # incl. the log_std slot with the gate bookkeeping folded
             # in) — narrow fp32 identity-head Gaussian policies (the
             # bench config)
-            use_mega = False
-            if kind == "gaussian" and ops.compute_bf16() == 0:
-                weights0, biases0, acts0 = _extract_layers(mlp)
-                brows0 = 32
-                whole_w0 = sum(w.shape[0] * (w.shape[1] + 1) for w in weights0)
-                use_mega = (
-                    acts0[-1] == 0  # identity head
-                    and len(weights0) + 1 <= 5
-                    and policy.log_std.numel() <= 64
-                    and max([obs0.shape[1]] + [w.shape[0] for w in weights0]) <= 64
-                    and ((3 + len(weights0)) * brows0 * 68 + whole_w0) * 4
-                    <= 100 * 1024
-                )
+            use_mega = _mega_eligible(policy, kind, obs0)
             if use_mega:
                 from rl_replicas_amd.ops.fused_adam import adam_arg_lists
 
@@ -554,14 +566,7 @@ class _GraphedValueLoop:
             # DO_FWD stages L extra activation tiles in LDS — mirror
             # the C++ budget gate so deep narrow nets fall back to the
             # separate-forward form instead of tripping the TORCH_CHECK
-            # (backward tiles are 32 rows at every batch: bwd_fused_rows)
-            brows = 32
-            whole_w = sum(
-                w.shape[0] * (w.shape[1] + 1) for w in _extract_layers(mlp)[0]
-            )
-            lds_ok = ((3 + len(_extract_layers(mlp)[0])) * brows * 68
-                      + whole_w) * 4 <= 100 * 1024
-            fp32 = ops.compute_bf16() == 0 and lds_ok
+            fp32 = ops.compute_bf16() == 0 and _fwd_in_kernel_fits(weights0)
             dummy = torch.empty(0, device=obs0.device)
 
             def body():
@@ -642,6 +647,108 @@ class _GraphedValueLoop:
         return float(losses.mean())
 
 
+class _GraphedPPOTwin:
+    """A whole PPO epoch's update — policy loop, value loop and their
+    epilogues — as ONE graph, with policy iteration i and value iteration
+    i sharing two launches (gaussian_ppo_value_twin_iter).
+
+    The two loops are independent (advantages and returns are computed
+    before either runs; neither net reads the other), so pairing them
+    changes no result: every launch runs each net's own arithmetic.  A
+    gate-frozen policy half returns at once inside a launch the value
+    half needs anyway, so the KL early stop no longer calls for chunked
+    capture with a host readback per chunk.  Requires P <= V; the V - P
+    tail runs value-only iterations through value_mlp_backward."""
+
+    def __init__(self, algo, obs0: Tensor, actions0: Tensor, adv0: Tensor,
+                 old_logp0: Tensor, returns0: Tensor):
+        from rl_replicas_amd.ops.fused_adam import adam_arg_lists
+
+        ext = ops._load_extension()
+        policy, vf = algo.policy, algo.value_function
+        pmlp, vmlp = _mlp_of(policy), vf.network
+        dev = obs0.device
+        self.obs = obs0.clone()
+        self.actions = actions0.clone()
+        self.adv = adv0.clone()
+        self.old_logp = old_logp0.clone()
+        self.returns = returns0.clone()
+        clip = float(algo.clip_range)
+        thr = 1.5 * float(algo.max_kl_divergence)
+        num_p = int(algo.num_policy_gradients)
+        num_v = int(algo.num_value_gradients)
+        assert 1 <= num_p <= num_v
+        self.gate = torch.ones(1, device=dev)
+        self.kl_final = torch.zeros(1, device=dev)
+        self.loss0 = torch.zeros(1, device=dev)
+        self.iters_done = torch.zeros(1, device=dev)
+        scratch_loss = torch.zeros(1, device=dev)
+
+        pw, pb, pacts = _extract_layers(pmlp)
+        pm, pv, pstep, php = adam_arg_lists(policy.optimizer, pw, pb)
+        state = [p.data for p in policy.parameters()]
+        state += _ensure_adam_state(policy.optimizer)
+        ls_state = policy.optimizer.state[policy.log_std]
+        ls_m, ls_v = ls_state["exp_avg"], ls_state["exp_avg_sq"]
+
+        vw, vb, vacts = _extract_layers(vmlp)
+        vm, vv, vstep, vhp = adam_arg_lists(vf.optimizer, vw, vb)
+        state += [p.data for p in vf.parameters()]
+        state += _ensure_adam_state(vf.optimizer)
+        fb = int(ext.value_loss_partials_blocks(obs0.shape[0]))
+        self.partials = torch.zeros(num_v, fb, device=dev)
+        dummy = torch.empty(0, device=dev)
+
+        def body():
+            self.gate.fill_(1.0)
+            self.iters_done.zero_()
+            for i in range(num_p):
+                ext.gaussian_ppo_value_twin_iter(
+                    self.obs, list(pw), list(pb), pacts, self.actions,
+                    self.old_logp, self.adv, policy.log_std.data, clip, pm,
+                    pv, ls_m, ls_v, pstep, *php, float(i), self.gate,
+                    self.kl_final, self.iters_done, thr,
+                    self.loss0 if i == 0 else scratch_loss, i == 0,
+                    self.obs, list(vw), list(vb), vacts, self.returns,
+                    self.partials[i], vm, vv, vstep, *vhp, float(i),
+                )
+            for i in range(num_p, num_v):
+                ext.value_mlp_backward(
+                    self.obs, list(vw), list(vb), [], dummy, vacts,
+                    self.returns, 0, self.partials[i], vm, vv, vstep, *vhp,
+                    float(i), True,
+                )
+            # policy epilogue: the final executed iteration's KL is still
+            # pending; after it iters_done IS the executed-update count
+            kl = ext.gaussian_kl(_forward_only(pmlp, self.obs), self.actions,
+                                 policy.log_std.data, self.old_logp)
+            ext.ppo_gate_update_(self.gate, kl, self.kl_final,
+                                 self.iters_done, thr)
+            policy.optimizer.bump_steps_by(self.iters_done)
+            vf.optimizer.bump_steps(float(num_v))
+            return ext.value_loss_finalize(self.partials, fb)
+
+        self.loop = _CapturedLoop(body, state)
+
+    def run(self, algo, obs, actions, advantages, old_logp, returns):
+        self.obs.copy_(obs)
+        self.actions.copy_(actions.view(self.actions.shape))
+        self.adv.copy_(advantages)
+        self.old_logp.copy_(old_logp)
+        self.returns.copy_(returns)
+        losses = self.loop.replay()
+        iters = int(self.iters_done)
+        if iters < algo.num_policy_gradients:
+            logger.info(
+                "Early stopping at update %d due to reaching max KL divergence.",
+                iters - 1,
+            )
+        return {
+            "policy/loss": float(self.loss0[0]),
+            "policy/kl_divergence": float(self.kl_final[0]),
+        }, float(losses.mean())
+
+
 def _get_cached_graph(algo, attr: str, key, builder):
     cached = getattr(algo, attr, None)
     if cached is not None and cached[0] == key:
@@ -651,13 +758,10 @@ def _get_cached_graph(algo, attr: str, key, builder):
     return graph
 
 
-def ppo_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[str, float]:
-    """The reference PPO policy-update loop (ppo.py:173-183) on the
-    fused kernel path; returns the same metric dict."""
-    ext = ops._load_extension()
+def _ppo_prelude(algo, obs: Tensor, actions: Tensor, advantages: Tensor):
+    """Kernel-layout inputs, the pre-update diagnostics and old_logp."""
     policy = algo.policy
     kind = _policy_kind(policy)
-    mlp = _mlp_of(policy)
     obs = obs.contiguous()
     if kind == "gaussian":
         actions_k = actions.contiguous().view(obs.shape[0], -1)
@@ -669,6 +773,78 @@ def ppo_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[s
 
     with torch.no_grad():
         old_logp = _old_logp(algo.old_policy, kind, obs, actions_k)
+    return kind, obs, actions_k, advantages, diagnostics, old_logp
+
+
+def ppo_twin_eligible(algo, obs: Tensor) -> bool:
+    """Whether ppo_value_twin_update applies: the mega policy iteration
+    and the fp32 narrow in-kernel-forward value iteration are both
+    eligible, both optimizers are FusedAdam, graphs are on, the loops
+    capture whole (no per-iteration collectives) and P <= V.
+    RL_REPLICAS_AMD_PPO_TWIN=0 selects the separate loops."""
+    import os
+
+    if os.environ.get("RL_REPLICAS_AMD_PPO_TWIN", "1") == "0":
+        return False
+    policy = algo.policy
+    if not supported(policy, obs) or value_mode(algo, obs) != "narrow":
+        return False
+    if not 1 <= int(algo.num_policy_gradients) <= int(algo.num_value_gradients):
+        return False
+    if not (_graphs_enabled(algo) and _graphs_enabled_value(algo)) or _dp_active(algo):
+        return False
+    if not _mega_eligible(policy, _policy_kind(policy), obs):
+        return False
+    vweights = _extract_layers(algo.value_function.network)[0]
+    if not _fwd_in_kernel_fits(vweights):
+        return False
+    # the twin reduce exists for the LDS-staged form only
+    ext = ops._load_extension()
+    fb = int(ext.value_loss_partials_blocks(obs.shape[0]))
+    pweights = _extract_layers(_mlp_of(policy))[0]
+    grand_p = sum(w.numel() + w.shape[0] for w in pweights) + policy.log_std.numel()
+    grand_v = sum(w.numel() + w.shape[0] for w in vweights)
+    return bool(ext.reduce_adam_is_staged(fb, grand_p)
+                and ext.reduce_adam_is_staged(fb, grand_v))
+
+
+def ppo_value_twin_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor,
+                          returns: Tensor):
+    """ppo_update and value_update of one epoch as one graph replay
+    (_GraphedPPOTwin); returns (policy metric dict, mean value loss), the
+    same values the separate loops give.  Caller checks ppo_twin_eligible."""
+    policy = algo.policy
+    kind, obs, actions_k, advantages, diagnostics, old_logp = _ppo_prelude(
+        algo, obs, actions, advantages
+    )
+    returns = returns.contiguous()
+    key = (tuple(obs.shape), tuple(actions_k.shape),
+           int(algo.num_policy_gradients), int(algo.num_value_gradients),
+           tuple(id(p) for p in policy.parameters()),
+           tuple(id(p) for p in algo.value_function.parameters()))
+    graphed = _get_cached_graph(
+        algo, "_ppo_twin_graph", key,
+        lambda: _GraphedPPOTwin(algo, obs, actions_k, advantages, old_logp, returns),
+    )
+    metrics, value_loss = graphed.run(algo, obs, actions_k, advantages, old_logp,
+                                      returns)
+    algo.old_policy.load_state_dict(policy.state_dict())
+    return {
+        "policy/loss": metrics["policy/loss"],
+        **diagnostics,
+        "policy/kl_divergence": metrics["policy/kl_divergence"],
+    }, value_loss
+
+
+def ppo_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[str, float]:
+    """The reference PPO policy-update loop (ppo.py:173-183) on the
+    fused kernel path; returns the same metric dict."""
+    ext = ops._load_extension()
+    policy = algo.policy
+    mlp = _mlp_of(policy)
+    kind, obs, actions_k, advantages, diagnostics, old_logp = _ppo_prelude(
+        algo, obs, actions, advantages
+    )
 
     if _graphs_enabled(algo):
         split = _dp_active(algo)

@@ -37,6 +37,12 @@ inline int bwd_fused_rows(int batch) { (void)batch; return 32; }
 __global__ void mlp_grad_reduce_onepass_f32(ReduceAllArgs a);
 void launch_mlp_grad_reduce_adam(const ReduceAdamArgs& a, long grand,
                                  hipStream_t stream);
+void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
+                               int n_blocks, int rows, hipStream_t stream);
+bool mlp_reduce_adam_is_staged(int n_blocks, long grand);
+void launch_mlp_grad_reduce_adam_twin(const ReduceAdamArgs& pol, long grand_pol,
+                                      const ReduceAdamArgs& val, long grand_val,
+                                      hipStream_t stream);
 void launch_mlp_layer_fwd_wide(const float* x, const float* W, const float* B,
                                float* out, int batch, int in_d, int out_d,
                                int act, hipStream_t stream);
@@ -135,19 +141,18 @@ void check_f32_gpu(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e));    \
   } while (0)
 
-// merged reduce+Adam launch (optional fast path of mlp_backward /
-// value_mlp_backward): m/v are ordered [weights..., biases...]
-void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
-                        const std::vector<torch::Tensor>& biases,
-                        const std::vector<int64_t>& totals, const float* ws,
-                        long stride, int n_blocks, int64_t grand,
-                        const std::vector<torch::Tensor>& m,
-                        const std::vector<torch::Tensor>& v,
-                        const torch::Tensor& step, double lr, double beta1,
-                        double beta2, double eps, double weight_decay,
-                        double step_delta,
-                        const c10::optional<torch::Tensor>& gate,
-                        hipStream_t stream) {
+// argument block of the merged reduce+Adam kernels for one net: m/v are
+// ordered [weights..., biases...]
+ReduceAdamArgs fill_reduce_adam(const std::vector<torch::Tensor>& weights,
+                                const std::vector<torch::Tensor>& biases,
+                                const std::vector<int64_t>& totals,
+                                const float* ws, long stride, int n_blocks,
+                                const std::vector<torch::Tensor>& m,
+                                const std::vector<torch::Tensor>& v,
+                                const torch::Tensor& step, double lr,
+                                double beta1, double beta2, double eps,
+                                double weight_decay, double step_delta,
+                                const c10::optional<torch::Tensor>& gate) {
   const int L = (int)weights.size();
   TORCH_CHECK((int)m.size() == 2 * L && (int)v.size() == 2 * L,
               "adam m/v must be [weights..., biases...] (2L tensors)");
@@ -174,8 +179,86 @@ void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
   ra.weight_decay = (float)weight_decay;
   ra.step_delta = (float)step_delta;
   ra.gate = gate.has_value() ? gate->data_ptr<float>() : nullptr;
+  return ra;
+}
+
+// merged reduce+Adam launch (optional fast path of mlp_backward /
+// value_mlp_backward)
+void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
+                        const std::vector<torch::Tensor>& biases,
+                        const std::vector<int64_t>& totals, const float* ws,
+                        long stride, int n_blocks, int64_t grand,
+                        const std::vector<torch::Tensor>& m,
+                        const std::vector<torch::Tensor>& v,
+                        const torch::Tensor& step, double lr, double beta1,
+                        double beta2, double eps, double weight_decay,
+                        double step_delta,
+                        const c10::optional<torch::Tensor>& gate,
+                        hipStream_t stream) {
+  const ReduceAdamArgs ra =
+      fill_reduce_adam(weights, biases, totals, ws, stride, n_blocks, m, v,
+                       step, lr, beta1, beta2, eps, weight_decay, step_delta,
+                       gate);
   launch_mlp_grad_reduce_adam(ra, (long)grand, stream);
   HIP_OK(hipGetLastError());
+}
+
+// flat layout of one net's gradient partials: the layers' (od*id + od)
+// segments in layer order; whole_w = floats of the padded whole-net LDS
+// weight image of the fused backward kernels
+struct NetLayout {
+  std::vector<int64_t> totals, layer_off;
+  int64_t grand = 0;
+  size_t whole_w = 0;
+  int max_width = 0;
+};
+
+NetLayout net_layout(const torch::Tensor& x,
+                     const std::vector<torch::Tensor>& weights) {
+  const int L = (int)weights.size();
+  NetLayout n;
+  n.totals.resize(L);
+  n.layer_off.resize(L);
+  n.max_width = (int)x.size(1);
+  for (int l = 0; l < L; ++l) {
+    n.totals[l] = (int64_t)weights[l].size(0) * weights[l].size(1) + weights[l].size(0);
+    n.layer_off[l] = n.grand;
+    n.grand += n.totals[l];
+    n.whole_w += (size_t)weights[l].size(0) * (weights[l].size(1) + 1);
+    n.max_width = std::max(n.max_width, (int)weights[l].size(0));
+  }
+  return n;
+}
+
+// dynamic LDS of the whole-net fused backward: 3 tiles (dZ ping-pong + x),
+// plus one activation tile per layer when the forward runs in the kernel
+size_t fused_bwd_lds(int L, int brows, size_t whole_w, bool fwd_in_kernel) {
+  const size_t act_tiles = (size_t)(fwd_in_kernel ? 3 + L : 3);
+  return (act_tiles * brows * 68 + whole_w) * 4;
+}
+
+// whole-net fused-backward argument block with h[] unset (the in-kernel
+// forward keeps activations in LDS); ws_stride = flat elems per partial row
+MLPBwdArgs fill_bwd_args(const torch::Tensor& x,
+                         const std::vector<torch::Tensor>& weights,
+                         const std::vector<torch::Tensor>& biases,
+                         const std::vector<int64_t>& acts,
+                         const NetLayout& n, int64_t ws_stride) {
+  const int L = (int)weights.size();
+  MLPBwdArgs ba{};
+  ba.n_layers = L;
+  ba.batch = (int)x.size(0);
+  ba.ws_stride = ws_stride;
+  ba.dims[0] = (int)x.size(1);
+  for (int l = 0; l < L; ++l) {
+    ba.w[l] = weights[l].data_ptr<float>();
+    ba.h[l] = nullptr;
+    ba.b[l] = biases[l].data_ptr<float>();
+    ba.dims[l + 1] = (int)weights[l].size(0);
+    ba.acts[l] = (int)acts[l];
+    ba.layer_off[l] = (int)n.layer_off[l];
+  }
+  return ba;
 }
 
 // (ROWS, MAXW) tile selection for the templated MLP kernels.
@@ -660,25 +743,15 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
   TORCH_CHECK((int)weights[L - 1].size(0) == 1 && acts[L - 1] == 0,
               "value_mlp_backward needs a 1-output identity head");
   const int batch = (int)x.size(0);
-  int max_width = (int)x.size(1);
-  for (int l = 0; l < L; ++l)
-    max_width = std::max(max_width, (int)weights[l].size(0));
-  TORCH_CHECK(max_width <= 64, "value_mlp_backward supports narrow nets only");
+  const NetLayout net = net_layout(x, weights);
+  TORCH_CHECK(net.max_width <= 64, "value_mlp_backward supports narrow nets only");
   auto opts = x.options();
   auto stream = current_stream();
 
-  std::vector<int64_t> totals(L), layer_off(L);
-  int64_t grand = 0;
-  for (int l = 0; l < L; ++l) {
-    totals[l] = (int64_t)weights[l].size(0) * weights[l].size(1) + weights[l].size(0);
-    layer_off[l] = grand;
-    grand += totals[l];
-  }
-  size_t whole_w = 0;
-  for (auto& w : weights) whole_w += (size_t)w.size(0) * (w.size(1) + 1);
+  const std::vector<int64_t>& totals = net.totals;
+  const int64_t grand = net.grand;
   const int brows = bwd_fused_rows(batch);
-  const size_t act_tiles = (size_t)(fwd_in_kernel ? 3 + L : 3);
-  const size_t fused_lds = (act_tiles * brows * 68 + whole_w) * 4;
+  const size_t fused_lds = fused_bwd_lds(L, brows, net.whole_w, fwd_in_kernel);
   TORCH_CHECK(fused_lds <= 100 * 1024, "net too large for fused value backward");
 
   const int fb = (batch + brows - 1) / brows;
@@ -692,22 +765,12 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
   torch::Tensor loss_partials = deferred ? *partials_out : torch::empty({fb}, opts);
   torch::Tensor scalars = torch::empty({1}, opts);
   std::vector<torch::Tensor> dws(L), dbs(L);
-  MLPBwdArgs ba{};
-  ba.n_layers = L;
-  ba.batch = batch;
-  ba.ws_stride = grand;
-  ba.dims[0] = (int)x.size(1);
+  MLPBwdArgs ba = fill_bwd_args(x, weights, biases, acts, net, grand);
   for (int l = 0; l < L; ++l) {
-    ba.w[l] = weights[l].data_ptr<float>();
     // fwd_in_kernel: activations never exist in HBM — the kernel
     // computes them into LDS (hidden/final_out are ignored)
-    ba.h[l] = fwd_in_kernel
-                  ? nullptr
-                  : (l == L - 1 ? final_out : hidden[l]).data_ptr<float>();
-    ba.b[l] = biases[l].data_ptr<float>();
-    ba.dims[l + 1] = (int)weights[l].size(0);
-    ba.acts[l] = (int)acts[l];
-    ba.layer_off[l] = (int)layer_off[l];
+    if (!fwd_in_kernel)
+      ba.h[l] = (l == L - 1 ? final_out : hidden[l]).data_ptr<float>();
     dws[l] = torch::empty({(int)weights[l].size(0), (int)weights[l].size(1)}, opts);
     dbs[l] = torch::empty({(int)weights[l].size(0)}, opts);
   }
@@ -1118,6 +1181,103 @@ void ppo_gate_update_(torch::Tensor gate, torch::Tensor kl,
 //      kl_final, iters_done and the iteration-0 loss.
 // Narrow fp32 identity-head Gaussian policies only (the bench config).
 // The returned tensor is the (empty) dx slot.
+namespace {
+
+// everything one Gaussian-PPO policy iteration launches with: the fused
+// kernel's argument blocks, the reduce+Adam block (log_std pseudo-layer
+// and gate bookkeeping included) and the buffers they point into
+struct PolicyIterBlocks {
+  MLPBwdArgs ba;
+  GaussSeedArgs ga;
+  ReduceAdamArgs ra;
+  torch::Tensor ws, loss_partials, kl_partials;
+  size_t fused_lds;
+  int fb, brows;
+  int64_t grand_ls;
+};
+
+PolicyIterBlocks build_policy_iter(
+    const torch::Tensor& x, const std::vector<torch::Tensor>& weights,
+    const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
+    const torch::Tensor& actions, const torch::Tensor& old_logp,
+    const torch::Tensor& advantages, const torch::Tensor& log_std, double clip,
+    const std::vector<torch::Tensor>& adam_m,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& ls_m,
+    const torch::Tensor& ls_v, const torch::Tensor& adam_step, double lr,
+    double beta1, double beta2, double eps, double weight_decay,
+    double step_delta, const torch::Tensor& gate, const torch::Tensor& kl_final,
+    const torch::Tensor& iters_done, double thr, const torch::Tensor& loss_out,
+    bool first_iter) {
+  const int L = (int)weights.size();
+  check_f32_gpu(x, "x");
+  const int batch = (int)x.size(0);
+  const int D = (int)weights[L - 1].size(0);
+  TORCH_CHECK(acts[L - 1] == 0, "needs an identity head");
+  TORCH_CHECK(L + 1 <= MLP_MAX_LAYERS, "too many layers for the log_std slot");
+  TORCH_CHECK(D <= 64, "action dim must fit one LDS row");
+  const NetLayout net = net_layout(x, weights);
+  TORCH_CHECK(net.max_width <= 64, "narrow nets only");
+  auto opts = x.options();
+
+  PolicyIterBlocks pb;
+  pb.grand_ls = net.grand + D;  // + dlog_std pseudo-layer
+  pb.brows = bwd_fused_rows(batch);
+  pb.fused_lds = fused_bwd_lds(L, pb.brows, net.whole_w, true);
+  TORCH_CHECK(pb.fused_lds <= 100 * 1024, "net too large for the fused iter");
+  pb.fb = (batch + pb.brows - 1) / pb.brows;
+
+  pb.ws = torch::empty({(int64_t)pb.fb, pb.grand_ls}, opts);
+  pb.loss_partials = torch::empty({pb.fb}, opts);
+  pb.kl_partials = torch::empty({pb.fb}, opts);
+
+  pb.ba = fill_bwd_args(x, weights, biases, acts, net, pb.grand_ls);
+  GaussSeedArgs& ga = pb.ga;
+  ga = GaussSeedArgs{};
+  ga.actions = actions.data_ptr<float>();
+  ga.old_logp = old_logp.data_ptr<float>();
+  ga.adv = advantages.data_ptr<float>();
+  ga.log_std = log_std.data_ptr<float>();
+  ga.kl_partials = pb.kl_partials.data_ptr<float>();
+  ga.dls_off = (int)net.grand;
+  ga.clip = (float)clip;
+  // a frozen iteration skips the fused kernel.  The first iteration never
+  // gates and its loss partials are always read, so it always runs.
+  ga.skip_gate = first_iter ? nullptr : gate.data_ptr<float>();
+
+  for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
+    check_f32_gpu(*t, "gate/kl_final/iters_done/loss_out");
+    TORCH_CHECK(t->numel() == 1, "gate bookkeeping scalars must have 1 element");
+  }
+  ReduceAdamArgs& ra = pb.ra;
+  ra = fill_reduce_adam(weights, biases, net.totals, pb.ws.data_ptr<float>(),
+                        pb.grand_ls, pb.fb, adam_m, adam_v, adam_step, lr,
+                        beta1, beta2, eps, weight_decay, step_delta, gate);
+  ra.n_layers = L + 1;
+  // log_std pseudo-layer: bias-only (wsize 0)
+  ra.pw[L] = nullptr;
+  ra.pb[L] = log_std.data_ptr<float>();
+  ra.mw[L] = nullptr;
+  ra.mb[L] = ls_m.data_ptr<float>();
+  ra.vw[L] = nullptr;
+  ra.vb[L] = ls_v.data_ptr<float>();
+  ra.total[L] = D;
+  ra.wsize[L] = 0;
+  // gate bookkeeping block: every workgroup derives the open/closed
+  // decision itself from the partials, workgroup 0 records it
+  ra.kl_partials = pb.kl_partials.data_ptr<float>();
+  ra.loss_partials = pb.loss_partials.data_ptr<float>();
+  ra.gate_rw = gate.data_ptr<float>();
+  ra.kl_final = kl_final.data_ptr<float>();
+  ra.iters_done = iters_done.data_ptr<float>();
+  ra.loss_out = loss_out.data_ptr<float>();
+  ra.inv_b = 1.f / (float)batch;
+  ra.thr = (float)thr;
+  ra.first_iter = first_iter ? 1 : 0;
+  return pb;
+}
+
+}  // namespace
+
 torch::Tensor gaussian_ppo_policy_iter(
     torch::Tensor x, std::vector<torch::Tensor> weights,
     std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
@@ -1128,122 +1288,96 @@ torch::Tensor gaussian_ppo_policy_iter(
     double weight_decay, double step_delta, torch::Tensor gate,
     torch::Tensor kl_final, torch::Tensor iters_done, double thr,
     torch::Tensor loss_out, bool first_iter) {
-  const int L = (int)weights.size();
-  check_f32_gpu(x, "x");
-  const int batch = (int)x.size(0);
-  const int D = (int)weights[L - 1].size(0);
-  TORCH_CHECK(acts[L - 1] == 0, "needs an identity head");
-  TORCH_CHECK(L + 1 <= MLP_MAX_LAYERS, "too many layers for the log_std slot");
-  TORCH_CHECK(D <= 64, "action dim must fit one LDS row");
-  int max_width = (int)x.size(1);
-  for (int l = 0; l < L; ++l)
-    max_width = std::max(max_width, (int)weights[l].size(0));
-  TORCH_CHECK(max_width <= 64, "narrow nets only");
-  auto opts = x.options();
+  const PolicyIterBlocks pb = build_policy_iter(
+      x, weights, biases, acts, actions, old_logp, advantages, log_std, clip,
+      adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
+      weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
+      first_iter);
   auto stream = current_stream();
-
-  std::vector<int64_t> totals(L), layer_off(L);
-  int64_t grand = 0;
-  for (int l = 0; l < L; ++l) {
-    totals[l] = (int64_t)weights[l].size(0) * weights[l].size(1) + weights[l].size(0);
-    layer_off[l] = grand;
-    grand += totals[l];
-  }
-  const int64_t grand_ls = grand + D;  // + dlog_std pseudo-layer
-  size_t whole_w = 0;
-  for (auto& w : weights) whole_w += (size_t)w.size(0) * (w.size(1) + 1);
-  const int brows = bwd_fused_rows(batch);
-  const size_t fused_lds = (((size_t)3 + L) * brows * 68 + whole_w) * 4;
-  TORCH_CHECK(fused_lds <= 100 * 1024, "net too large for the fused iter");
-  const int fb = (batch + brows - 1) / brows;
-
-  torch::Tensor ws = torch::empty({(int64_t)fb, grand_ls}, opts);
-  torch::Tensor loss_partials = torch::empty({fb}, opts);
-  torch::Tensor kl_partials = torch::empty({fb}, opts);
-
-  MLPBwdArgs ba{};
-  ba.n_layers = L;
-  ba.batch = batch;
-  ba.ws_stride = grand_ls;
-  ba.dims[0] = (int)x.size(1);
-  for (int l = 0; l < L; ++l) {
-    ba.w[l] = weights[l].data_ptr<float>();
-    ba.h[l] = nullptr;
-    ba.b[l] = biases[l].data_ptr<float>();
-    ba.dims[l + 1] = (int)weights[l].size(0);
-    ba.acts[l] = (int)acts[l];
-    ba.layer_off[l] = (int)layer_off[l];
-  }
-  GaussSeedArgs ga{};
-  ga.actions = actions.data_ptr<float>();
-  ga.old_logp = old_logp.data_ptr<float>();
-  ga.adv = advantages.data_ptr<float>();
-  ga.log_std = log_std.data_ptr<float>();
-  ga.kl_partials = kl_partials.data_ptr<float>();
-  ga.dls_off = (int)grand;
-  ga.clip = (float)clip;
-  // a frozen iteration skips the fused kernel.  The first iteration never
-  // gates and its loss partials are always read, so it always runs.
-  ga.skip_gate = first_iter ? nullptr : gate.data_ptr<float>();
-
   // no input gradient: the update is fused, nobody reads dx
-  launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr, nullptr,
-                       ws.data_ptr<float>(), nullptr,
-                       loss_partials.data_ptr<float>(), fused_lds, fb, 0,
-                       stream, brows, 1, ga, 0);
+  launch_mlp_bwd_fused(pb.ba, x.data_ptr<float>(), nullptr, nullptr,
+                       pb.ws.data_ptr<float>(), nullptr,
+                       pb.loss_partials.data_ptr<float>(), pb.fused_lds, pb.fb,
+                       0, stream, pb.brows, 1, pb.ga, 0);
+  HIP_OK(hipGetLastError());
+  launch_mlp_grad_reduce_adam(pb.ra, (long)pb.grand_ls, stream);
+  HIP_OK(hipGetLastError());
+  return torch::empty({0}, x.options());  // dx slot: never computed here
+}
+
+// Policy iteration i and value iteration i of one PPO epoch in the SAME
+// two launches (the two loops are independent: neither reads what the
+// other writes):
+//   1. twin fused kernel, grid (fb, 2): the Gaussian-PPO half of
+//      gaussian_ppo_policy_iter and the fwd_in_kernel fused-Adam half of
+//      value_mlp_backward;
+//   2. twin reduce+Adam: the policy's gated update with its bookkeeping
+//      and the value net's ungated one.
+// Arguments are those of gaussian_ppo_policy_iter, then the value net's
+// (v_*).  v_partials_out is the caller's deferred loss-partials row.  Each
+// net's result is bitwise what its own binding gives.
+void gaussian_ppo_value_twin_iter(
+    torch::Tensor x, std::vector<torch::Tensor> weights,
+    std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
+    torch::Tensor actions, torch::Tensor old_logp, torch::Tensor advantages,
+    torch::Tensor log_std, double clip, std::vector<torch::Tensor> adam_m,
+    std::vector<torch::Tensor> adam_v, torch::Tensor ls_m, torch::Tensor ls_v,
+    torch::Tensor adam_step, double lr, double beta1, double beta2, double eps,
+    double weight_decay, double step_delta, torch::Tensor gate,
+    torch::Tensor kl_final, torch::Tensor iters_done, double thr,
+    torch::Tensor loss_out, bool first_iter, torch::Tensor v_x,
+    std::vector<torch::Tensor> v_weights, std::vector<torch::Tensor> v_biases,
+    std::vector<int64_t> v_acts, torch::Tensor returns,
+    torch::Tensor v_partials_out, std::vector<torch::Tensor> v_adam_m,
+    std::vector<torch::Tensor> v_adam_v, torch::Tensor v_adam_step,
+    double v_lr, double v_beta1, double v_beta2, double v_eps,
+    double v_weight_decay, double v_step_delta) {
+  TORCH_CHECK(v_x.data_ptr() == x.data_ptr() && v_x.sizes() == x.sizes(),
+              "the twin iteration needs the same x for both nets");
+  const PolicyIterBlocks pb = build_policy_iter(
+      x, weights, biases, acts, actions, old_logp, advantages, log_std, clip,
+      adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
+      weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
+      first_iter);
+
+  const int VL = (int)v_weights.size();
+  check_f32_gpu(returns, "returns");
+  TORCH_CHECK((int)returns.numel() == (int)x.size(0), "returns must be [batch]");
+  TORCH_CHECK((int)v_weights[VL - 1].size(0) == 1 && v_acts[VL - 1] == 0,
+              "the value half needs a 1-output identity head");
+  const NetLayout vnet = net_layout(x, v_weights);
+  TORCH_CHECK(vnet.max_width <= 64, "narrow nets only");
+  const size_t v_lds = fused_bwd_lds(VL, pb.brows, vnet.whole_w, true);
+  TORCH_CHECK(v_lds <= 100 * 1024, "value net too large for the fused iter");
+  check_f32_gpu(v_partials_out, "v_partials_out");
+  TORCH_CHECK(v_partials_out.numel() >= pb.fb, "v_partials_out too small");
+  TORCH_CHECK(mlp_reduce_adam_is_staged(pb.fb, (long)pb.grand_ls) &&
+                  mlp_reduce_adam_is_staged(pb.fb, (long)vnet.grand),
+              "the twin reduce needs both nets on the staged reduce");
+  torch::Tensor v_ws = torch::empty({(int64_t)pb.fb, vnet.grand}, x.options());
+
+  MLPBwdTwinArgs ta{};
+  ta.pol = pb.ba;
+  ta.gauss = pb.ga;
+  ta.pol_ws = pb.ws.data_ptr<float>();
+  ta.pol_loss_partials = pb.loss_partials.data_ptr<float>();
+  ta.val = fill_bwd_args(x, v_weights, v_biases, v_acts, vnet, vnet.grand);
+  ta.val_ws = v_ws.data_ptr<float>();
+  ta.returns = returns.data_ptr<float>();
+  ta.val_loss_partials = v_partials_out.data_ptr<float>();
+  ta.x = x.data_ptr<float>();
+  auto stream = current_stream();
+  launch_mlp_bwd_fused_twin(ta, std::max(pb.fused_lds, v_lds), pb.fb, pb.brows,
+                            stream);
   HIP_OK(hipGetLastError());
 
-  TORCH_CHECK((int)adam_m.size() == 2 * L && (int)adam_v.size() == 2 * L);
-  for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
-    check_f32_gpu(*t, "gate/kl_final/iters_done/loss_out");
-    TORCH_CHECK(t->numel() == 1, "gate bookkeeping scalars must have 1 element");
-  }
-  ReduceAdamArgs ra{};
-  ra.ws = ws.data_ptr<float>();
-  ra.stride = grand_ls;
-  ra.n_layers = L + 1;
-  ra.n_blocks = fb;
-  for (int l = 0; l < L; ++l) {
-    ra.pw[l] = weights[l].data_ptr<float>();
-    ra.pb[l] = biases[l].data_ptr<float>();
-    ra.mw[l] = adam_m[l].data_ptr<float>();
-    ra.mb[l] = adam_m[L + l].data_ptr<float>();
-    ra.vw[l] = adam_v[l].data_ptr<float>();
-    ra.vb[l] = adam_v[L + l].data_ptr<float>();
-    ra.total[l] = (int)totals[l];
-    ra.wsize[l] = (int)(weights[l].size(0) * weights[l].size(1));
-  }
-  // log_std pseudo-layer: bias-only (wsize 0)
-  ra.pw[L] = nullptr;
-  ra.pb[L] = log_std.data_ptr<float>();
-  ra.mw[L] = nullptr;
-  ra.mb[L] = ls_m.data_ptr<float>();
-  ra.vw[L] = nullptr;
-  ra.vb[L] = ls_v.data_ptr<float>();
-  ra.total[L] = D;
-  ra.wsize[L] = 0;
-  ra.step = adam_step.data_ptr<float>();
-  ra.lr = (float)lr;
-  ra.beta1 = (float)beta1;
-  ra.beta2 = (float)beta2;
-  ra.eps = (float)eps;
-  ra.weight_decay = (float)weight_decay;
-  ra.step_delta = (float)step_delta;
-  ra.gate = gate.data_ptr<float>();
-  // gate bookkeeping block: every workgroup derives the open/closed
-  // decision itself from the partials, workgroup 0 records it
-  ra.kl_partials = kl_partials.data_ptr<float>();
-  ra.loss_partials = loss_partials.data_ptr<float>();
-  ra.gate_rw = gate.data_ptr<float>();
-  ra.kl_final = kl_final.data_ptr<float>();
-  ra.iters_done = iters_done.data_ptr<float>();
-  ra.loss_out = loss_out.data_ptr<float>();
-  ra.inv_b = 1.f / (float)batch;
-  ra.thr = (float)thr;
-  ra.first_iter = first_iter ? 1 : 0;
-  launch_mlp_grad_reduce_adam(ra, (long)grand_ls, stream);
+  const ReduceAdamArgs vra = fill_reduce_adam(
+      v_weights, v_biases, vnet.totals, v_ws.data_ptr<float>(), vnet.grand,
+      pb.fb, v_adam_m, v_adam_v, v_adam_step, v_lr, v_beta1, v_beta2, v_eps,
+      v_weight_decay, v_step_delta, c10::nullopt);
+  launch_mlp_grad_reduce_adam_twin(pb.ra, (long)pb.grand_ls, vra,
+                                   (long)vnet.grand, stream);
   HIP_OK(hipGetLastError());
-  return torch::empty({0}, opts);  // dx slot: never computed here
 }
 
 void counter_add_(torch::Tensor ctr, int64_t delta) {
@@ -1293,6 +1427,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "device-side KL early-stop gate bookkeeping (gfx950)");
   m.def("gaussian_ppo_policy_iter", &gaussian_ppo_policy_iter,
         "one 2-kernel Gaussian-PPO policy iteration (gfx950)");
+  m.def("gaussian_ppo_value_twin_iter", &gaussian_ppo_value_twin_iter,
+        "PPO policy + value iteration in one twin kernel pair (gfx950)");
+  m.def("reduce_adam_is_staged",
+        [](int64_t n_blocks, int64_t grand) {
+          return mlp_reduce_adam_is_staged((int)n_blocks, (long)grand);
+        },
+        "whether the reduce+Adam launch takes the LDS-staged kernel");
   m.def("segmented_gae", &segmented_gae, "segmented GAE+returns scan (gfx950)");
   m.def("normalize", &normalize, "fused mean/std normalize (gfx950)");
   m.def("q_target", &q_target, "fused Q-learning target (gfx950)");

@@ -191,6 +191,21 @@ struct GaussSeedArgs {
   const float* skip_gate;
 };
 
+// twin PPO update launch (mlp_bwd_fused_twin_f32): the Gaussian-PPO policy
+// half and the value-MSE half of one update iteration, each with its own
+// net, workspace and partials; both read the same x.  ~0.5 KB by value.
+struct MLPBwdTwinArgs {
+  MLPBwdArgs pol;
+  GaussSeedArgs gauss;
+  float* pol_ws;
+  float* pol_loss_partials;  // [n_blocks]
+  MLPBwdArgs val;
+  float* val_ws;
+  const float* returns;      // [B]
+  float* val_loss_partials;  // [n_blocks] (the caller's deferred-loss row)
+  const float* x;            // [B, dims[0]] of both nets
+};
+
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)
 struct ReplayGatherArgs {
   const float* obs;   // [cap, O] ring storage
