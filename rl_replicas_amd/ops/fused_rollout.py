@@ -7,6 +7,14 @@ rollout (optional lockstep reset / state carry, then steps x
 [forward -> sample -> env step], then one RNG-counter bump) is captured
 once and replayed as a single hipGraph per epoch.
 
+For the flagship shape (fp32, widths and obs dim <= 64) the 3 x steps
+kernels of that graph are ONE persistent kernel (`ppo_rollout_fused`):
+each workgroup carries 16 env rows through every step with weights and
+state in LDS, using the same device functions, Philox offsets and
+element indices as the three kernels, so the buffers hold the same bytes
+(`fused_kernel_eligible`; RL_REPLICAS_AMD_ROLLOUT_FUSED=0 keeps the
+three-kernel body).
+
 Randomness across replays: by-value Philox offsets are frozen at
 capture, so every RNG kernel adds a device-resident int64 counter
 (`offset_ctr`) to its offset; the graph's last node advances the
@@ -46,6 +54,34 @@ def supported(policy, env) -> bool:
     return mlp is not None and _extract_layers(mlp) is not None
 
 
+def fused_kernel_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
+    """Whether the epoch runs as ONE persistent kernel (ppo_rollout_fused,
+    rollout_fused_kernels.hip) instead of steps x 3 kernels: fp32 compute,
+    a Gaussian policy without action clipping (the only kind `supported`
+    admits), every width and the obs dim <= 64, and the net + env image
+    within the kernel's LDS budget.  RL_REPLICAS_AMD_ROLLOUT_FUSED=0
+    selects the three-kernel body."""
+    import os
+
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
+        return False
+    if ops.compute_bf16() != 0:
+        return False
+    ext = ops._load_extension()
+    weights, _, _ = _extract_layers(fop._mlp_of(policy))
+    O, A = int(env.A.shape[0]), int(env.B.shape[0])
+    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
+    max_layers, max_width, max_cuts, max_lds = ext.ppo_rollout_fused_limits()
+    if (len(weights) > max_layers or max(dims) > max_width or dims[0] != O
+            or dims[-1] != A or policy.log_std.numel() != A
+            or len(cuts) > max_cuts):
+        return False
+    if any(t.dtype != torch.float32 for t in (*weights, policy.log_std)):
+        return False
+    return ext.ppo_rollout_fused_lds_bytes(dims, O, A) <= max_lds
+
+
 def make_counter(device) -> torch.Tensor:
     """Device RNG counter; base 2^40 keeps the graph streams clear of the
     host-side offsets the eager paths use under the same seeds."""
@@ -54,7 +90,8 @@ def make_counter(device) -> torch.Tensor:
 
 class GraphedRollout:
     """One captured epoch: [reset | state carry] + steps x (mlp_forward ->
-    gaussian_sample -> synthetic_env_step) + counter bump."""
+    gaussian_sample -> synthetic_env_step) + counter bump; or, when
+    `fused_kernel_eligible`, ppo_rollout_fused + counter bump."""
 
     def __init__(self, policy, env, steps: int, cuts: Tuple[int, ...],
                  start_with_reset: bool, ctr: torch.Tensor):
@@ -80,6 +117,19 @@ class GraphedRollout:
         log_std = policy.log_std
         cset = {c: j for j, c in enumerate(cuts)}
         compute_bf16 = ops.compute_bf16()
+
+        self.fused = fused_kernel_eligible(policy, env, cuts)
+
+        def body_fused():
+            # 2 nodes: the persistent kernel carries every 16-row tile
+            # through all steps; it reads ctr once and the bump follows
+            ext.ppo_rollout_fused(
+                list(weights), list(biases), acts, log_std.data, env.A, env.B,
+                env.w, env.noise, policy_seed, env_seed, list(cuts),
+                start_with_reset, self.ctr, self.obs_full, self.act_buf,
+                self.rew_buf, self.cut_final,
+            )
+            ext.counter_add_(self.ctr, 2 * steps + 1)
 
         def body():
             if start_with_reset:
@@ -107,7 +157,7 @@ class GraphedRollout:
         # warmup advances ctr (and the state carry buffer); snapshot/restore
         # so the first replay starts exactly where the eager world left off
         state = [self.ctr] if start_with_reset else [self.ctr, self.obs_full]
-        self.loop = fop._CapturedLoop(body, state)
+        self.loop = fop._CapturedLoop(body_fused if self.fused else body, state)
 
     def replay(self) -> None:
         self.loop.replay()

@@ -102,6 +102,8 @@ __global__ void synthetic_env_reset_kernel(float* s_out, int total,
                                            const unsigned long long* offset_ptr);
 __global__ void counter_add_kernel(unsigned long long* ctr,
                                    unsigned long long delta);
+size_t ppo_rollout_fused_lds_bytes(const int* dims, int n_layers, int O, int A);
+void launch_ppo_rollout_fused(const RolloutFusedArgs& a, hipStream_t stream);
 __global__ void segmented_gae_kernel(const float* rewards, const float* values,
                                      const float* last_values, const int* offsets,
                                      const int* dones, float* advantages,
@@ -1389,7 +1391,124 @@ void counter_add_(torch::Tensor ctr, int64_t delta) {
   HIP_OK(hipGetLastError());
 }
 
+// LDS budget of the persistent rollout kernel: the same 100 KiB bound the
+// whole-net-staged MLP kernels use (pick_wstage)
+#define ROLLOUT_FUSED_MAX_LDS (100 * 1024)
+
+// dims = [O, hidden..., A] of the policy net
+int64_t ppo_rollout_fused_lds_bytes_py(std::vector<int64_t> dims, int64_t O,
+                                       int64_t A) {
+  const int L = (int)dims.size() - 1;
+  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
+  int d[MLP_MAX_LAYERS + 1];
+  for (int l = 0; l <= L; ++l) d[l] = (int)dims[l];
+  return (int64_t)ppo_rollout_fused_lds_bytes(d, L, (int)O, (int)A);
+}
+
+// whole-epoch rollout in one launch (rollout_fused_kernels.hip): writes
+// obs_full[0..steps], act_buf, rew_buf and cut_final[j] for cuts[j];
+// reads the RNG counter, never advances it (counter_add_ follows)
+void ppo_rollout_fused(std::vector<torch::Tensor> weights,
+                       std::vector<torch::Tensor> biases,
+                       std::vector<int64_t> acts, torch::Tensor log_std,
+                       torch::Tensor envA, torch::Tensor envB, torch::Tensor envw,
+                       double sigma, int64_t policy_seed, int64_t env_seed,
+                       std::vector<int64_t> cuts, bool start_with_reset,
+                       torch::Tensor ctr, torch::Tensor obs_full,
+                       torch::Tensor act_buf, torch::Tensor rew_buf,
+                       torch::Tensor cut_final) {
+  const int L = (int)weights.size();
+  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
+  TORCH_CHECK((int)biases.size() == L && (int)acts.size() == L,
+              "weights/biases/acts length mismatch");
+  check_f32_gpu(obs_full, "obs_full");
+  check_f32_gpu(act_buf, "act_buf");
+  check_f32_gpu(rew_buf, "rew_buf");
+  check_f32_gpu(cut_final, "cut_final");
+  check_f32_gpu(log_std, "log_std");
+  check_f32_gpu(envA, "env A");
+  check_f32_gpu(envB, "env B");
+  check_f32_gpu(envw, "env w");
+  TORCH_CHECK(obs_full.dim() == 3 && obs_full.size(0) >= 2, "obs_full must be [steps+1, N, O]");
+  RolloutFusedArgs a{};
+  a.steps = (int)obs_full.size(0) - 1;
+  a.N = (int)obs_full.size(1);
+  a.O = (int)obs_full.size(2);
+  a.A = (int)log_std.numel();
+  TORCH_CHECK(a.N >= 1 && a.O >= 1 && a.O <= ROLLOUT_MAX_WIDTH && a.A >= 1 &&
+                  a.A <= ROLLOUT_MAX_WIDTH,
+              "ppo_rollout_fused: obs/action dims must be in [1, ", ROLLOUT_MAX_WIDTH, "]");
+  TORCH_CHECK(act_buf.dim() == 3 && act_buf.size(0) == a.steps &&
+                  act_buf.size(1) == a.N && act_buf.size(2) == a.A,
+              "act_buf must be [steps, N, A]");
+  TORCH_CHECK(rew_buf.dim() == 2 && rew_buf.size(0) == a.steps && rew_buf.size(1) == a.N,
+              "rew_buf must be [steps, N]");
+  TORCH_CHECK(envA.dim() == 2 && envA.size(0) == a.O && envA.size(1) == a.O &&
+                  envB.dim() == 2 && envB.size(0) == a.A && envB.size(1) == a.O &&
+                  envw.numel() == a.O,
+              "env matrices must be A[O,O], B[A,O], w[O]");
+  a.n_layers = L;
+  a.dims[0] = a.O;
+  for (int l = 0; l < L; ++l) {
+    check_f32_gpu(weights[l], "weight");
+    check_f32_gpu(biases[l], "bias");
+    a.dims[l + 1] = (int)weights[l].size(0);
+    TORCH_CHECK(weights[l].dim() == 2 && (int)weights[l].size(1) == a.dims[l],
+                "weight shape mismatch");
+    TORCH_CHECK((int)biases[l].numel() == a.dims[l + 1], "bias shape mismatch");
+    TORCH_CHECK(a.dims[l + 1] <= ROLLOUT_MAX_WIDTH,
+                "ppo_rollout_fused: layer width must be <= ", ROLLOUT_MAX_WIDTH);
+    a.w[l] = weights[l].data_ptr<float>();
+    a.b[l] = biases[l].data_ptr<float>();
+    a.acts[l] = (int)acts[l];
+  }
+  TORCH_CHECK(a.dims[L] == a.A, "policy head width must equal the action dim");
+  TORCH_CHECK(ppo_rollout_fused_lds_bytes(a.dims, L, a.O, a.A) <= ROLLOUT_FUSED_MAX_LDS,
+              "ppo_rollout_fused: net + env image exceeds the LDS budget");
+  a.n_cuts = (int)cuts.size();
+  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "ppo_rollout_fused: too many cuts");
+  TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
+                  cut_final.size(1) == a.N && cut_final.size(2) == a.O,
+              "cut_final must be [n_cuts, N, O]");
+  for (int c = 0; c < a.n_cuts; ++c) {
+    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < a.steps, "cut step out of range");
+    a.cut_step[c] = (int)cuts[c];
+  }
+  a.log_std = log_std.data_ptr<float>();
+  a.envA = envA.data_ptr<float>();
+  a.envB = envB.data_ptr<float>();
+  a.envw = envw.data_ptr<float>();
+  a.obs_full = obs_full.data_ptr<float>();
+  a.act_buf = act_buf.data_ptr<float>();
+  a.rew_buf = rew_buf.data_ptr<float>();
+  a.cut_final = cut_final.data_ptr<float>();
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.start_with_reset = start_with_reset ? 1 : 0;
+  a.sigma = (float)sigma;
+  a.policy_seed = (uint64_t)policy_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_ppo_rollout_fused(a, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("ppo_rollout_fused", &ppo_rollout_fused,
+        "whole-epoch PPO rollout in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"),
+        py::arg("log_std"), py::arg("env_A"), py::arg("env_B"), py::arg("env_w"),
+        py::arg("sigma"), py::arg("policy_seed"), py::arg("env_seed"),
+        py::arg("cuts"), py::arg("start_with_reset"), py::arg("ctr"),
+        py::arg("obs_full"), py::arg("act_buf"), py::arg("rew_buf"),
+        py::arg("cut_final"));
+  m.def("ppo_rollout_fused_lds_bytes", &ppo_rollout_fused_lds_bytes_py,
+        "dynamic LDS of ppo_rollout_fused for a net [O, ..., A]");
+  m.def("ppo_rollout_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
+                                      ROLLOUT_MAX_CUTS, ROLLOUT_FUSED_MAX_LDS};
+        },
+        "(max layers, max width / obs dim, max cuts, LDS budget in bytes) of "
+        "ppo_rollout_fused");
   m.def("mlp_forward", &mlp_forward, "fused MLP forward (gfx950)",
         py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("acts"),
         py::arg("save_hidden"), py::arg("compute_bf16") = 0);

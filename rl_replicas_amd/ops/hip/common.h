@@ -206,6 +206,36 @@ struct MLPBwdTwinArgs {
   const float* x;            // [B, dims[0]] of both nets
 };
 
+// persistent rollout kernel (rollout_fused_kernels.hip): one workgroup
+// carries ROLLOUT_ROWS env rows through all `steps` iterations of
+// forward -> Gaussian sample -> env transition.
+#define ROLLOUT_ROWS 16
+#define ROLLOUT_MAX_WIDTH 64  // widest layer / obs dim (one wave per env row)
+#define ROLLOUT_LDSW (ROLLOUT_MAX_WIDTH + 4)  // LDS row stride of the 16-row tiles
+#define ROLLOUT_MAX_CUTS 16   // lockstep truncation cuts per captured epoch
+struct RolloutFusedArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;
+  const float* log_std;  // [A]
+  const float* envA;     // [O, O]
+  const float* envB;     // [A, O]
+  const float* envw;     // [O]
+  float* obs_full;       // [steps + 1, N, O]; slot `steps` is the carry
+  float* act_buf;        // [steps, N, A]
+  float* rew_buf;        // [steps, N]
+  float* cut_final;      // [n_cuts, N, O] pre-reset successors, cut order
+  const unsigned long long* ctr;  // device RNG counter (read once)
+  int cut_step[ROLLOUT_MAX_CUTS];
+  int n_cuts;
+  int N, O, A, steps;
+  int start_with_reset;  // 1: Philox reset; 0: continue from the carry slot
+  float sigma;           // env dynamics noise
+  uint64_t policy_seed, env_seed;
+};
+
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)
 struct ReplayGatherArgs {
   const float* obs;   // [cap, O] ring storage

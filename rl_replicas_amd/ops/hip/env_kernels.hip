@@ -12,6 +12,7 @@
 // launch-latency: fewer launches IS the optimization.
 #include "common.h"
 #include "philox.h"
+#include "rollout_steps.h"
 
 // grid = N blocks of 64 threads (one wave per env row).
 // s_out: next live state (post-autoreset when do_reset).
@@ -31,38 +32,13 @@ __global__ __launch_bounds__(64) void synthetic_env_step_kernel(
   const float* a = actions + (long)row * Adim;
   const int o = threadIdx.x;
 
-  float r_part = 0.f;
-  float out_o = 0.f;
-  if (o < O) {
-    float acc = 0.f;
-    for (int k = 0; k < O; ++k) acc += s[k] * A[k * O + o];
-    for (int j = 0; j < Adim; ++j) {
-      const float aj = fminf(fmaxf(a[j], -1.f), 1.f);
-      acc += aj * Bm[j * O + o];
-    }
-    if (sigma > 0.f)
-      acc += sigma * philox_normal(seed, offset, (uint32_t)(row * O + o));
-    out_o = tanhf(acc);
-    final_out[(long)row * O + o] = out_o;
-    r_part = out_o * w[o];
-  }
-  if (o == 0) {
-    float pen = 0.f;
-    for (int j = 0; j < Adim; ++j) {
-      const float aj = fminf(fmaxf(a[j], -1.f), 1.f);
-      pen += aj * aj;
-    }
-    r_part -= 0.1f * pen;
-  }
-  const float rsum = wave_reduce_sum(r_part);
+  // the row arithmetic is shared with the persistent rollout kernel
+  float out_o, s_next, rsum;
+  synthetic_env_row(s, a, A, Bm, w, row, o, O, Adim, sigma, seed, offset,
+                    do_reset, &out_o, &s_next, &rsum);
+  if (o < O) final_out[(long)row * O + o] = out_o;
   if (o == 0) reward[row] = rsum;
-  if (o < O) {
-    // offset+1 is the autoreset noise stream (host bumps the counter by 2
-    // on reset steps so streams never collide)
-    s_out[(long)row * O + o] =
-        do_reset ? 0.1f * philox_normal(seed, offset + 1, (uint32_t)(row * O + o))
-                 : out_o;
-  }
+  if (o < O) s_out[(long)row * O + o] = s_next;
 }
 
 // fresh init states: s = 0.1 * eps  (SyntheticEnv._init_state)

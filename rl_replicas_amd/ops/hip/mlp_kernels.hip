@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "rollout_steps.h"
 
 // ---------------------------------------------------------------------------
 // helpers
@@ -123,28 +124,9 @@ __global__ __launch_bounds__(256) void fused_mlp_fwd_f32_t(
       const int j = jt + i;
       const bool jok = j < out_d;
       if (wstage_mode == 0) {
-        const float* wl = wlds + woff;
-        if constexpr (BF16) {
-          // bf16 compute: v_mfma_f32_16x16x32_bf16, fp32 accumulate;
-          // fragments built from the fp32 LDS images with RNE converts
-          for (int k0 = 0; k0 < in_d; k0 += 32) {
-            bf16x8 af, bf;
-            #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const int kk = k0 + k * 8 + e;
-              af[e] = f32_to_bf16((kk < in_d) ? buf_in[(wr0 + i) * LDSW + kk] : 0.f);
-              bf[e] = f32_to_bf16((jok && kk < in_d) ? wl[j * wrow + kk] : 0.f);
-            }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
-          }
-        } else {
-          for (int k0 = 0; k0 < in_d; k0 += 4) {
-            const int kk = k0 + k;
-            float a = (kk < in_d) ? buf_in[(wr0 + i) * LDSW + kk] : 0.f;
-            float bv = (jok && kk < in_d) ? wl[j * wrow + kk] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-          }
-        }
+        // shared with the persistent rollout kernel (rollout_steps.h)
+        acc = mlp_fwd_tile_lds<LDSW, BF16>(buf_in, wlds + woff, wrow, in_d,
+                                           wr0 + i, k, j, jok);
       } else if (wstage_mode == 2) {
         // direct global W reads (wide nets at large grids: the L2
         // misses hide behind cross-wave parallelism)
@@ -173,14 +155,7 @@ __global__ __launch_bounds__(256) void fused_mlp_fwd_f32_t(
           wave_lds_fence();  // reads done before next chunk overwrites
         }
       }
-      if (jok) {
-        const float bias = B[j];
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wr0 + (lane >> 4) * 4 + r;
-          buf_out[row * LDSW + j] = act_apply(act, acc[r] + bias);
-        }
-      }
+      mlp_fwd_tile_epilogue<LDSW>(acc, B, act, j, jok, wr0, lane, buf_out);
     }
     __syncthreads();
 

@@ -1,0 +1,114 @@
+// Per-row arithmetic of one rollout step, shared by the three stand-alone
+// kernels (fused_mlp_fwd_f32_t, gaussian_sample_kernel,
+// synthetic_env_step_kernel) and the persistent rollout kernel
+// (rollout_fused_kernels.hip).  Every caller inlines the SAME expressions
+// in the SAME order, so both routes produce the same bytes; the operands
+// may live in global memory or in LDS.
+#pragma once
+#include "common.h"
+#include "philox.h"
+
+// One 16x16 output tile of a Linear layer from LDS-resident operands:
+// activations buf_in[row][LDSW], weights wl[out][wrow] (padded image).
+// Lane (i = lane & 15, k = lane >> 4) feeds A[arow][k0 + k] and
+// W[j][k0 + k]; the k0 order is the accumulation order.
+template <int LDSW, bool BF16>
+DEV_INLINE f32x4 mlp_fwd_tile_lds(const float* buf_in, const float* wl, int wrow,
+                                  int in_d, int arow, int k, int j, bool jok) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (BF16) {
+    // bf16 compute: v_mfma_f32_16x16x32_bf16, fp32 accumulate;
+    // fragments built from the fp32 LDS images with RNE converts
+    for (int k0 = 0; k0 < in_d; k0 += 32) {
+      bf16x8 af, bf;
+      #pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int kk = k0 + k * 8 + e;
+        af[e] = f32_to_bf16((kk < in_d) ? buf_in[arow * LDSW + kk] : 0.f);
+        bf[e] = f32_to_bf16((jok && kk < in_d) ? wl[j * wrow + kk] : 0.f);
+      }
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
+    }
+  } else {
+    for (int k0 = 0; k0 < in_d; k0 += 4) {
+      const int kk = k0 + k;
+      float a = (kk < in_d) ? buf_in[arow * LDSW + kk] : 0.f;
+      float bv = (jok && kk < in_d) ? wl[j * wrow + kk] : 0.f;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+    }
+  }
+  return acc;
+}
+
+// bias + activation epilogue of one output tile into buf_out[row][LDSW]
+// (C/D map: col = lane & 15, row = (lane >> 4) * 4 + r)
+template <int LDSW>
+DEV_INLINE void mlp_fwd_tile_epilogue(f32x4 acc, const float* B, int act, int j,
+                                      bool jok, int wr0, int lane, float* buf_out) {
+  if (jok) {
+    const float bias = B[j];
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = wr0 + (lane >> 4) * 4 + r;
+      buf_out[row * LDSW + j] = act_apply(act, acc[r] + bias);
+    }
+  }
+}
+
+// one action element: mean + exp(log_std[d]) * z, z keyed by
+// (seed, offset, i); noise_scale >= 0 overrides sigma, limit >= 0 clips
+DEV_INLINE float gaussian_sample_elem(float mean, const float* log_std, int d,
+                                      uint64_t seed, uint64_t offset, uint32_t i,
+                                      float noise_scale, float limit) {
+  uint32_t r[4];
+  philox4(seed, offset, i, r);
+  float z0, z1;
+  box_muller(r[0], r[1], &z0, &z1);
+  const float sigma = noise_scale >= 0.f ? noise_scale : __expf(log_std[d]);
+  float a = mean + sigma * z0;
+  if (limit >= 0.f) a = fminf(fmaxf(a, -limit), limit);
+  return a;
+}
+
+// one env row on one wave: lane o owns state column o.
+//   out_o  : true successor state element (pre-reset)
+//   s_next : next live state element (autoreset draw when do_reset)
+//   rsum   : the row's reward (valid on lane 0)
+// All 64 lanes of the wave must call it (wave_reduce_sum).
+DEV_INLINE void synthetic_env_row(const float* s, const float* a, const float* A,
+                                  const float* Bm, const float* w, int row, int o,
+                                  int O, int Adim, float sigma, uint64_t seed,
+                                  uint64_t offset, int do_reset, float* out_o_p,
+                                  float* s_next_p, float* rsum_p) {
+  float r_part = 0.f;
+  float out_o = 0.f;
+  if (o < O) {
+    float acc = 0.f;
+    for (int k = 0; k < O; ++k) acc += s[k] * A[k * O + o];
+    for (int j = 0; j < Adim; ++j) {
+      const float aj = fminf(fmaxf(a[j], -1.f), 1.f);
+      acc += aj * Bm[j * O + o];
+    }
+    if (sigma > 0.f)
+      acc += sigma * philox_normal(seed, offset, (uint32_t)(row * O + o));
+    out_o = tanhf(acc);
+    r_part = out_o * w[o];
+  }
+  if (o == 0) {
+    float pen = 0.f;
+    for (int j = 0; j < Adim; ++j) {
+      const float aj = fminf(fmaxf(a[j], -1.f), 1.f);
+      pen += aj * aj;
+    }
+    r_part -= 0.1f * pen;
+  }
+  *rsum_p = wave_reduce_sum(r_part);
+  float s_next = out_o;
+  if (o < O && do_reset) {
+    // offset+1 is the autoreset noise stream (host bumps the counter by 2
+    // on reset steps so streams never collide)
+    s_next = 0.1f * philox_normal(seed, offset + 1, (uint32_t)(row * O + o));
+  }
+  *out_o_p = out_o;
+  *s_next_p = s_next;
+}

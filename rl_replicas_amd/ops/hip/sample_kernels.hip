@@ -8,6 +8,7 @@
 // under hipGraph capture) with Box-Muller for normals.
 #include "common.h"
 #include "philox.h"
+#include "rollout_steps.h"
 
 // actions = mean + exp(log_std) * z, with optional clip to [-limit, limit]
 // (limit < 0 disables clipping; noise_scale overrides sigma when >= 0,
@@ -23,15 +24,8 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(
   if (offset_ptr) offset += *offset_ptr;
   const int total = B * D;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    uint32_t r[4];
-    philox4(seed, offset, (uint32_t)i, r);
-    float z0, z1;
-    box_muller(r[0], r[1], &z0, &z1);
-    const int d = i % D;
-    const float sigma = noise_scale >= 0.f ? noise_scale : __expf(log_std[d]);
-    float a = mean[i] + sigma * z0;
-    if (limit >= 0.f) a = fminf(fmaxf(a, -limit), limit);
-    out[i] = a;
+    out[i] = gaussian_sample_elem(mean[i], log_std, i % D, seed, offset,
+                                  (uint32_t)i, noise_scale, limit);
   }
 }
 

@@ -1,0 +1,141 @@
+"""The persistent rollout kernel (gpu-marked): ppo_rollout_fused carries
+each 16-row tile through the whole epoch in one launch.  Its per-row
+arithmetic is the shared code of the three stand-alone kernels, so every
+comparison is torch.equal between a sampler built with the fused kernel and
+one built with RL_REPLICAS_AMD_ROLLOUT_FUSED=0 from identical seeds and
+initial weights — no tolerance.
+
+N = 5 (less than one tile), 16 (exactly one), 37 (two full tiles and a
+5-row tail).  Nets: the bench net [17,64,32,6] and [5,8,3], whose dims are
+no multiple of 4 or 16.  Cut patterns come from a small horizon: horizon 2
+with 3 steps cuts mid-epoch, horizon 3 with 3 steps cuts on the last step,
+horizon 2 with 4 steps cuts twice.  Carried across calls (is_continuous),
+horizon 2 with 3 steps alternates the patterns (1,) and (0, 2), so the
+carry slot crosses two captured graphs."""
+import pytest
+import torch
+import torch.nn as nn
+
+pytestmark = pytest.mark.gpu
+
+DEVICE = "cuda"
+AWKWARD_ID = "RolloutFusedAwkward-v0"
+NETS = {
+    "bench": ("HalfCheetah-v4", [17, 64, 32, 6]),
+    "awkward": (AWKWARD_ID, [5, 8, 3]),
+}
+# name: (horizon, steps, cut patterns expected over three epochs when
+# every epoch resets, ... when state is carried)
+CASES = {
+    "no_cut": (1000, 3, {()}, {()}),
+    "cut_middle": (2, 3, {(1,)}, {(1,), (0, 2)}),
+    "cut_last": (3, 3, {(2,)}, {(2,)}),
+    "two_cuts": (2, 4, {(1, 3)}, {(1, 3)}),
+}
+CTR_BASE = 1 << 40
+
+
+def _register_awkward():
+    from rl_replicas_amd.envs.core import register, registered_ids
+    from rl_replicas_amd.envs.synthetic import SyntheticEnv
+
+    if AWKWARD_ID not in registered_ids():
+        register(AWKWARD_ID, lambda **kw: SyntheticEnv(AWKWARD_ID, 5, 3, **kw))
+
+
+def _rollouts(monkeypatch, fused, net, n_envs, horizon, steps, continuous,
+              epochs=3, mutate_before=None):
+    """Run `epochs` sampler calls; per call: (graph, obs_full, act_buf,
+    rew_buf, cut_finals, counter), all cloned."""
+    from rl_replicas_amd import envs, ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.policies import GaussianPolicy
+    from rl_replicas_amd.samplers import DeviceSampler
+
+    _register_awkward()
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1" if fused else "0")
+    env_id, dims = NETS[net] if isinstance(net, str) else net
+    torch.manual_seed(77)
+    denv = envs.DeviceVectorEnv(env_id, num_envs=n_envs, device=DEVICE,
+                                max_episode_steps=horizon)
+    pnet = MLP(dims).to(DEVICE)
+    log_std = nn.Parameter(-0.5 * torch.ones(dims[-1], device=DEVICE))
+    policy = GaussianPolicy(
+        pnet, ops.make_adam(list(pnet.parameters()) + [log_std], lr=3e-4), log_std
+    )
+    sampler = DeviceSampler(denv, seed=5, is_continuous=continuous)
+    out = []
+    for e in range(epochs):
+        if mutate_before == e:
+            with torch.no_grad():
+                for p in pnet.parameters():
+                    p.mul_(1.25).add_(0.01)
+                log_std.add_(0.3)
+        sampler.sample(n_envs * steps, policy)
+        (g,) = [g for g in sampler._graphs.values()
+                if g.obs_full[steps].data_ptr() == sampler._obs.data_ptr()]
+        torch.cuda.synchronize()
+        out.append((g, g.obs_full.clone(), g.act_buf.clone(), g.rew_buf.clone(),
+                    [c.clone() for c in g.final_tensors()],
+                    int(sampler._graph_ctr.item())))
+    return out
+
+
+def _assert_same(fused_run, plain_run, steps):
+    for e, (f, p) in enumerate(zip(fused_run, plain_run)):
+        assert f[0].fused and not p[0].fused
+        assert f[0].cuts == p[0].cuts
+        assert f[5] == p[5] == CTR_BASE + (e + 1) * (2 * steps + 1)
+        assert torch.equal(f[1], p[1]), f"obs_full differs in epoch {e}"
+        assert torch.equal(f[2], p[2]), f"act_buf differs in epoch {e}"
+        assert torch.equal(f[3], p[3]), f"rew_buf differs in epoch {e}"
+        assert len(f[4]) == len(p[4]) == len(f[0].cuts)
+        for j, (cf, cp) in enumerate(zip(f[4], p[4])):
+            assert torch.equal(cf, cp), f"cut_final[{j}] differs in epoch {e}"
+        assert torch.isfinite(f[1]).all() and torch.isfinite(f[2]).all()
+
+
+@pytest.mark.parametrize("continuous", [False, True], ids=["reset", "carry"])
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("net", list(NETS))
+@pytest.mark.parametrize("n_envs", [5, 16, 37])
+def test_fused_equals_three_kernel_body(monkeypatch, n_envs, net, case, continuous):
+    """Three consecutive replays: obs_full (carry slot included), act_buf,
+    rew_buf, every cut_final[j] and the RNG counter are equal."""
+    horizon, steps, cuts_reset, cuts_carry = CASES[case]
+    f = _rollouts(monkeypatch, True, net, n_envs, horizon, steps, continuous)
+    p = _rollouts(monkeypatch, False, net, n_envs, horizon, steps, continuous)
+    _assert_same(f, p, steps)
+    assert {tuple(r[0].cuts) for r in f} == (cuts_carry if continuous else cuts_reset)
+    # the replays draw fresh randomness
+    assert not torch.equal(f[0][2], f[1][2])
+    for e in (1, 2):
+        # a carried epoch starts from the previous epoch's carry slot
+        assert f[e][0].start_with_reset == (not continuous)
+        if continuous:
+            assert torch.equal(f[e][1][0], f[e - 1][1][steps])
+
+
+@pytest.mark.parametrize("continuous", [False, True], ids=["reset", "carry"])
+@pytest.mark.parametrize("net", list(NETS))
+def test_fused_reads_weights_by_pointer(monkeypatch, net, continuous):
+    """Weights and log_std changed in place between replays of the same
+    captured graph: the kernel sees the new values."""
+    f = _rollouts(monkeypatch, True, net, 37, 2, 3, continuous, mutate_before=1)
+    p = _rollouts(monkeypatch, False, net, 37, 2, 3, continuous, mutate_before=1)
+    _assert_same(f, p, 3)
+    same = _rollouts(monkeypatch, True, net, 37, 2, 3, continuous)
+    assert torch.equal(same[0][2], f[0][2])
+    assert not torch.equal(same[1][2], f[1][2])
+
+
+def test_outside_gate_takes_three_kernel_body(monkeypatch):
+    """A 128-wide hidden layer does not fit the kernel's tiles: the old
+    body runs and still samples."""
+    runs = _rollouts(monkeypatch, True, ("HalfCheetah-v4", [17, 128, 6]), 37, 2, 3,
+                     True, epochs=2)
+    for g, obs, act, rew, finals, _ in runs:
+        assert not g.fused
+        assert torch.isfinite(obs).all() and torch.isfinite(act).all()
+        assert torch.isfinite(rew).all() and len(finals) == len(g.cuts)
+        assert act.abs().sum() > 0 and obs[1:].abs().sum() > 0
