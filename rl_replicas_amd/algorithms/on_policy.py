@@ -109,7 +109,8 @@ class OnPolicyAlgorithm(AlgorithmBase):
         if isinstance(flat["observations"], Tensor):
             # device-resident rollout (DeviceSampler): nothing to upload
             obs = flat["observations"].to(device)
-            actions = flat["actions"].to(device)
+            # fp32 like the numpy path below (discrete actions arrive int64)
+            actions = flat["actions"].to(device=device, dtype=torch.float32)
             rewards = flat["rewards"].to(device)
             last_obs = flat["last_observations"].to(device)
             return self._finish_batch(flat, obs, actions, rewards, last_obs, device)

@@ -2,7 +2,7 @@ from .spaces import Box, Discrete, Space
 from .core import Env, EnvSpec, make, register, registered_ids
 from .classic import CartPoleEnv, PendulumEnv
 from .synthetic import MUJOCO_SHAPES, SyntheticEnv
-from .device import DevicePendulumEnv, DeviceVectorEnv
+from .device import DeviceCartPoleEnv, DevicePendulumEnv, DeviceVectorEnv
 from .subproc import SubprocVectorEnv
 from .vector import SerialVectorEnv, VectorEnv
 
@@ -24,4 +24,5 @@ __all__ = [
     "SubprocVectorEnv",
     "DeviceVectorEnv",
     "DevicePendulumEnv",
+    "DeviceCartPoleEnv",
 ]

@@ -219,3 +219,133 @@ class DevicePendulumEnv:
 
     def close(self) -> None:
         pass
+
+
+class DeviceCartPoleEnv:
+    """CartPole-v1 as N device-resident instances with PER-INSTANCE
+    termination, truncation and autoreset (`VectorEnv.step` semantics).
+
+    Unlike the lockstep envs above, `step` returns a `done` TENSOR: episode
+    boundaries are data.  The carry is public and updated in place —
+    `state` fp64 [N,4] (x, x_dot, theta, theta_dot; the host env keeps fp64
+    state and casts to fp32 only for the observation) and `elapsed` int32
+    [N] — so captured graphs and the persistent rollout kernel
+    (`ops/fused_rollout.py::GraphedCartPoleRollout`) read and write the
+    same storage the eager path uses.
+
+    On GPU with the extension, `step`/`reset` are one kernel each
+    (`cartpole_env_step` / `cartpole_env_reset`, env_kernels.hip); otherwise
+    the same arithmetic runs as torch fp64 ops.  Dynamics follow
+    `classic.CartPoleEnv._step_b` (constants, expression order); only the
+    init-state RNG stream differs (Philox / torch generator vs numpy).
+    """
+
+    def __init__(self, num_envs: int, device="cpu", max_episode_steps: Optional[int] = 500):
+        from .classic import CartPoleEnv
+        from .core import EnvSpec
+
+        base = CartPoleEnv()
+        self.num_envs = int(num_envs)
+        self.device = torch.device(device)
+        self.observation_space = base.observation_space
+        self.action_space = base.action_space
+        self.spec = EnvSpec("CartPole-v1", max_episode_steps=max_episode_steps)
+        self.state = torch.zeros(self.num_envs, 4, dtype=torch.float64, device=self.device)
+        self.elapsed = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
+        # same salt as DeviceVectorEnv: decorrelates the env stream from the
+        # policy's action-sampling stream keyed on the same torch seed
+        self._philox_seed = (torch.initial_seed() ^ 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+        self._philox_offset = 0
+
+    @property
+    def max_steps(self) -> int:
+        """Kernel-side horizon (0: no truncation)."""
+        return int(self.spec.max_episode_steps or 0)
+
+    def seed(self, seed: Optional[int]) -> None:
+        if seed is not None:
+            self._gen.manual_seed(int(seed))
+            self._philox_seed = (int(seed) ^ 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+            self._philox_offset = 0
+            self.action_space.seed(seed + 1000)  # VectorEnv.seed contract
+
+    def _wants_hip(self) -> bool:
+        from rl_replicas_amd import ops
+
+        return self.device.type == "cuda" and ops.wants_hip(self.state)
+
+    def _init_state(self) -> Tensor:
+        # the kernel's formula on a torch-generator uniform: strictly
+        # inside (-0.05, 0.05)
+        u = torch.rand(self.num_envs, 4, generator=self._gen, device=self.device,
+                       dtype=torch.float64)
+        r = torch.floor(u * 4294967296.0)
+        return -0.05 + 0.1 * ((r + 0.5) * (1.0 / 4294967296.0))
+
+    def reset(self, *, seed: Optional[int] = None) -> Tensor:
+        if seed is not None:
+            self.seed(seed)
+        if self._wants_hip():
+            from rl_replicas_amd import ops
+
+            obs = ops._load_extension().cartpole_env_reset(
+                self.state, self.elapsed, self._philox_seed, self._philox_offset
+            )
+            self._philox_offset += 1
+            return obs
+        self.state.copy_(self._init_state())
+        self.elapsed.zero_()
+        return self.state.float()
+
+    def step(self, actions: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """-> (obs [N,4], reward [N], done [N] bool, final_obs [N,4]).
+
+        `obs` is post-autoreset, `final_obs` the true successor (GAE
+        bootstrap); `done = terminated | truncated` per instance."""
+        if self._wants_hip():
+            from rl_replicas_amd import ops
+
+            obs, reward, done, final_obs = ops._load_extension().cartpole_env_step(
+                self.state, self.elapsed,
+                actions.reshape(-1).to(torch.int64).contiguous(), self.max_steps,
+                self._philox_seed, self._philox_offset,
+            )
+            self._philox_offset += 1
+            return obs, reward, done.bool(), final_obs
+
+        import math
+
+        x, x_dot, theta, theta_dot = self.state.unbind(dim=1)
+        force = torch.where(actions.reshape(-1).to(self.device) == 1, 10.0, -10.0).to(torch.float64)
+        total_mass = 1.0 + 0.1
+        polemass_length = 0.1 * 0.5
+        costheta = torch.cos(theta)
+        sintheta = torch.sin(theta)
+        temp = (force + polemass_length * (theta_dot * theta_dot) * sintheta) / total_mass
+        thetaacc = (9.8 * sintheta - costheta * temp) / (
+            0.5 * (4.0 / 3.0 - 0.1 * (costheta * costheta) / total_mass)
+        )
+        xacc = temp - polemass_length * thetaacc * costheta / total_mass
+        x = x + 0.02 * x_dot
+        x_dot = x_dot + 0.02 * xacc
+        theta = theta + 0.02 * theta_dot
+        theta_dot = theta_dot + 0.02 * thetaacc
+        new = torch.stack([x, x_dot, theta, theta_dot], dim=1)
+        terminated = (x.abs() > 2.4) | (theta.abs() > 12 * 2 * math.pi / 360)
+        elapsed = self.elapsed + 1
+        if self.spec.max_episode_steps is not None:
+            truncated = (elapsed >= self.spec.max_episode_steps) & ~terminated
+        else:
+            truncated = torch.zeros_like(terminated)
+        done = terminated | truncated
+        final_obs = new.float()
+        # every row draws (no host sync on `done.any()`); done rows keep it
+        self.state.copy_(torch.where(done[:, None], self._init_state(), new))
+        self.elapsed.copy_(torch.where(done, torch.zeros_like(elapsed), elapsed))
+        reward = torch.ones(self.num_envs, dtype=torch.float32, device=self.device)
+        return self.state.float(), reward, done, final_obs
+
+    def close(self) -> None:
+        pass

@@ -28,6 +28,12 @@ happens only when the epoch's lockstep-truncation pattern changes
 (bounded: the horizon/steps arithmetic cycles through at most two
 patterns when horizon % steps == 0, the benchmark shape).
 
+`GraphedCartPoleRollout` is the same construction for a
+CategoricalPolicy on `DeviceCartPoleEnv` (DeviceEpisodicSampler fast
+path): termination, truncation and autoreset are decided in-kernel per
+instance, so there are no cut patterns, and the persistent kernel is
+`cartpole_rollout_fused` (`cartpole_fused_eligible`).
+
 No reference counterpart (the reference samples one env serially on
 the host, batch_sampler.py:55-99).
 """
@@ -165,3 +171,114 @@ class GraphedRollout:
     def final_tensors(self) -> List[torch.Tensor]:
         """Per-cut bootstrap observations, in cut order."""
         return [self.cut_final[j] for j in range(len(self.cuts))]
+
+
+# ---------------------------------------------------------------------------
+# Categorical policy on the device CartPole env (DeviceEpisodicSampler)
+# ---------------------------------------------------------------------------
+def cartpole_supported(policy, env) -> bool:
+    """A CategoricalPolicy over an MLP on a GPU DeviceCartPoleEnv, with the
+    extension present and graphs enabled."""
+    from rl_replicas_amd.envs.device import DeviceCartPoleEnv
+
+    if not (isinstance(env, DeviceCartPoleEnv) and env.device.type == "cuda"
+            and ops.hip_available() and fop._graphs_common(None)
+            and fop._policy_kind(policy) == "categorical"):
+        return False
+    mlp = fop._mlp_of(policy)
+    return mlp is not None and _extract_layers(mlp) is not None
+
+
+def cartpole_fused_eligible(policy, env) -> bool:
+    """Whether the epoch runs as ONE persistent kernel (cartpole_rollout_fused,
+    cartpole_rollout_kernels.hip) instead of steps x 3 kernels: fp32 compute,
+    every width <= 64, the net image within the kernel's LDS budget.
+    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    import os
+
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
+        return False
+    if ops.compute_bf16() != 0:
+        return False
+    ext = ops._load_extension()
+    weights, _, _ = _extract_layers(fop._mlp_of(policy))
+    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
+    max_layers, max_width, max_lds = ext.cartpole_rollout_fused_limits()
+    if len(weights) > max_layers or max(dims) > max_width or dims[0] != 4:
+        return False
+    if any(w.dtype != torch.float32 for w in weights):
+        return False
+    return ext.cartpole_rollout_fused_lds_bytes(dims) <= max_lds
+
+
+class GraphedCartPoleRollout:
+    """One captured epoch on a DeviceCartPoleEnv: [cartpole_env_reset |
+    nothing] + steps x (mlp_forward -> categorical_sample ->
+    cartpole_env_step) + counter bump; or, when `cartpole_fused_eligible`,
+    cartpole_rollout_fused + counter bump.
+
+    Termination, truncation and autoreset are decided in-kernel, so there is
+    one graph per (steps, start_with_reset) and no cut patterns.  The env's
+    carry tensors (`env.state`, `env.elapsed`) are read and written in
+    place.  Philox offsets (both bodies): policy sample and autoreset of
+    step t at `t + ctr` (policy seed / env seed), epoch reset at
+    `steps + ctr`; the last node advances the counter by steps + 1."""
+
+    def __init__(self, policy, env, steps: int, start_with_reset: bool,
+                 ctr: torch.Tensor):
+        ext = ops._load_extension()
+        N = env.num_envs
+        dev = env.device
+        self.env = env
+        self.steps = steps
+        self.start_with_reset = start_with_reset
+        self.obs_full = torch.zeros(steps + 1, N, 4, device=dev)
+        self.final_obs = torch.zeros(steps, N, 4, device=dev)
+        self.act_buf = torch.zeros(steps, N, dtype=torch.int64, device=dev)
+        self.rew_buf = torch.zeros(steps, N, device=dev)
+        self.done_buf = torch.zeros(steps, N, dtype=torch.uint8, device=dev)
+        self.ctr = ctr
+        policy_seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
+        env_seed = env._philox_seed
+        max_steps = env.max_steps
+        weights, biases, acts = _extract_layers(fop._mlp_of(policy))
+        compute_bf16 = ops.compute_bf16()
+
+        self.fused = cartpole_fused_eligible(policy, env)
+
+        def body_fused():
+            ext.cartpole_rollout_fused(
+                list(weights), list(biases), acts, policy_seed, env_seed,
+                max_steps, start_with_reset, self.ctr, env.state, env.elapsed,
+                self.obs_full, self.final_obs, self.act_buf, self.rew_buf,
+                self.done_buf,
+            )
+            ext.counter_add_(self.ctr, steps + 1)
+
+        def body():
+            if start_with_reset:
+                ext.cartpole_env_reset(env.state, env.elapsed, env_seed, steps,
+                                       self.ctr, self.obs_full[0])
+            else:
+                self.obs_full[0].copy_(env.state)
+            for t in range(steps):
+                logits = ext.mlp_forward(self.obs_full[t], list(weights),
+                                         list(biases), acts, False, compute_bf16)[0]
+                ext.categorical_sample(logits, policy_seed, t, self.ctr,
+                                       self.act_buf[t])
+                ext.cartpole_env_step(
+                    env.state, env.elapsed, self.act_buf[t], max_steps, env_seed,
+                    t, self.ctr, self.obs_full[t + 1], self.final_obs[t],
+                    self.rew_buf[t], self.done_buf[t],
+                )
+            # past every offset used: sample/autoreset t (t<steps), reset steps
+            ext.counter_add_(self.ctr, steps + 1)
+
+        # warmup advances ctr and the env carry; snapshot/restore so the
+        # first replay starts exactly where the eager world left off
+        state = [self.ctr, env.state, env.elapsed]
+        self.loop = fop._CapturedLoop(body_fused if self.fused else body, state)
+
+    def replay(self) -> None:
+        self.loop.replay()

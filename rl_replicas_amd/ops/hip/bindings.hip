@@ -88,7 +88,19 @@ __global__ void gaussian_sample_kernel(const float* mean, const float* log_std,
                                        const unsigned long long* offset_ptr);
 __global__ void categorical_sample_kernel(const float* logits, int64_t* out,
                                           int B, int N, uint64_t seed,
-                                          uint64_t offset);
+                                          uint64_t offset,
+                                          const unsigned long long* offset_ptr);
+__global__ void cartpole_env_step_kernel(double* state, int* elapsed,
+                                         const int64_t* actions, float* obs,
+                                         float* final_obs, float* reward,
+                                         uint8_t* done, int N, int max_steps,
+                                         uint64_t seed, uint64_t offset,
+                                         const unsigned long long* offset_ptr);
+__global__ void cartpole_env_reset_kernel(double* state, int* elapsed, float* obs,
+                                          int N, uint64_t seed, uint64_t offset,
+                                          const unsigned long long* offset_ptr);
+size_t cartpole_rollout_fused_lds_bytes(const int* dims, int n_layers);
+void launch_cartpole_rollout_fused(const CartPoleRolloutArgs& a, hipStream_t stream);
 __global__ void synthetic_env_step_kernel(const float* state, const float* actions,
                                           const float* A, const float* Bm,
                                           const float* w, float* s_out,
@@ -1022,18 +1034,96 @@ torch::Tensor gaussian_sample(torch::Tensor mean, torch::Tensor log_std,
 }
 
 torch::Tensor categorical_sample(torch::Tensor logits, int64_t seed,
-                                 int64_t offset) {
+                                 int64_t offset,
+                                 c10::optional<torch::Tensor> offset_ctr,
+                                 c10::optional<torch::Tensor> out_opt) {
   check_f32_gpu(logits, "logits");
   const int B = (int)logits.size(0);
   const int N = (int)logits.size(1);
-  auto out = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  auto out = out_opt.has_value()
+                 ? *out_opt
+                 : torch::empty({B}, logits.options().dtype(torch::kInt64));
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+                  out.scalar_type() == torch::kInt64 && out.numel() == B,
+              "categorical_sample: out must be a contiguous int64 CUDA tensor [B]");
   hipLaunchKernelGGL(categorical_sample_kernel,
                      dim3(std::min(256, (B + 255) / 256)), dim3(256), 0,
                      current_stream(), logits.data_ptr<float>(),
                      out.data_ptr<int64_t>(), B, N, (uint64_t)seed,
-                     (uint64_t)offset);
+                     (uint64_t)offset, ctr_ptr(offset_ctr));
   HIP_OK(hipGetLastError());
   return out;
+}
+
+// CartPole carry tensors: state fp64 [N,4], elapsed int32 [N]
+static int check_cartpole_carry(const torch::Tensor& state,
+                                const torch::Tensor& elapsed) {
+  TORCH_CHECK(state.is_cuda() && state.is_contiguous() &&
+                  state.scalar_type() == torch::kFloat64 && state.dim() == 2 &&
+                  state.size(1) == 4,
+              "state must be a contiguous float64 CUDA tensor [N, 4]");
+  TORCH_CHECK(elapsed.is_cuda() && elapsed.is_contiguous() &&
+                  elapsed.scalar_type() == torch::kInt32 &&
+                  elapsed.numel() == state.size(0),
+              "elapsed must be a contiguous int32 CUDA tensor [N]");
+  return (int)state.size(0);
+}
+
+static void check_out(const torch::Tensor& t, torch::ScalarType dt, int64_t numel,
+                      const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == dt &&
+                  t.numel() == numel,
+              name, ": wrong device, dtype, layout or size");
+}
+
+// -> {obs, reward, done, final_obs}; state and elapsed are updated in place
+std::vector<torch::Tensor> cartpole_env_step(
+    torch::Tensor state, torch::Tensor elapsed, torch::Tensor actions,
+    int64_t max_steps, int64_t seed, int64_t offset,
+    c10::optional<torch::Tensor> offset_ctr, c10::optional<torch::Tensor> obs_opt,
+    c10::optional<torch::Tensor> final_opt, c10::optional<torch::Tensor> reward_opt,
+    c10::optional<torch::Tensor> done_opt) {
+  const int N = check_cartpole_carry(state, elapsed);
+  check_out(actions, torch::kInt64, N, "actions");
+  const auto f32 = state.options().dtype(torch::kFloat32);
+  auto obs = obs_opt.has_value() ? *obs_opt : torch::empty({N, 4}, f32);
+  auto fin = final_opt.has_value() ? *final_opt : torch::empty({N, 4}, f32);
+  auto reward = reward_opt.has_value() ? *reward_opt : torch::empty({N}, f32);
+  auto done = done_opt.has_value()
+                  ? *done_opt
+                  : torch::empty({N}, state.options().dtype(torch::kUInt8));
+  check_out(obs, torch::kFloat32, (int64_t)N * 4, "obs");
+  check_out(fin, torch::kFloat32, (int64_t)N * 4, "final_obs");
+  check_out(reward, torch::kFloat32, N, "reward");
+  check_out(done, torch::kUInt8, N, "done");
+  hipLaunchKernelGGL(cartpole_env_step_kernel,
+                     dim3(std::min(256, (N + 255) / 256)), dim3(256), 0,
+                     current_stream(), state.data_ptr<double>(),
+                     elapsed.data_ptr<int>(), actions.data_ptr<int64_t>(),
+                     obs.data_ptr<float>(), fin.data_ptr<float>(),
+                     reward.data_ptr<float>(), done.data_ptr<uint8_t>(), N,
+                     (int)max_steps, (uint64_t)seed, (uint64_t)offset,
+                     ctr_ptr(offset_ctr));
+  HIP_OK(hipGetLastError());
+  return {obs, reward, done, fin};
+}
+
+torch::Tensor cartpole_env_reset(torch::Tensor state, torch::Tensor elapsed,
+                                 int64_t seed, int64_t offset,
+                                 c10::optional<torch::Tensor> offset_ctr,
+                                 c10::optional<torch::Tensor> obs_opt) {
+  const int N = check_cartpole_carry(state, elapsed);
+  auto obs = obs_opt.has_value()
+                 ? *obs_opt
+                 : torch::empty({N, 4}, state.options().dtype(torch::kFloat32));
+  check_out(obs, torch::kFloat32, (int64_t)N * 4, "obs");
+  hipLaunchKernelGGL(cartpole_env_reset_kernel,
+                     dim3(std::min(256, (N + 255) / 256)), dim3(256), 0,
+                     current_stream(), state.data_ptr<double>(),
+                     elapsed.data_ptr<int>(), obs.data_ptr<float>(), N,
+                     (uint64_t)seed, (uint64_t)offset, ctr_ptr(offset_ctr));
+  HIP_OK(hipGetLastError());
+  return obs;
 }
 
 std::vector<torch::Tensor> synthetic_env_step(torch::Tensor state,
@@ -1491,7 +1581,108 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
   HIP_OK(hipGetLastError());
 }
 
+// LDS budget of the persistent CartPole kernel: the default per-workgroup
+// dynamic LDS limit (no opt-in attribute needed)
+#define CARTPOLE_ROLLOUT_MAX_LDS (64 * 1024)
+
+// dims = [4, hidden..., n_act] of the policy net
+int64_t cartpole_rollout_fused_lds_bytes_py(std::vector<int64_t> dims) {
+  const int L = (int)dims.size() - 1;
+  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
+  int d[MLP_MAX_LAYERS + 1];
+  for (int l = 0; l <= L; ++l) d[l] = (int)dims[l];
+  return (int64_t)cartpole_rollout_fused_lds_bytes(d, L);
+}
+
+// whole-epoch CartPole rollout in one launch (cartpole_rollout_kernels.hip):
+// writes obs_full[0..steps], final_obs, act_buf, rew_buf, done_buf and the
+// env carry; reads the RNG counter, never advances it (counter_add_ follows)
+void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
+                            std::vector<torch::Tensor> biases,
+                            std::vector<int64_t> acts, int64_t policy_seed,
+                            int64_t env_seed, int64_t max_steps,
+                            bool start_with_reset, torch::Tensor ctr,
+                            torch::Tensor state, torch::Tensor elapsed,
+                            torch::Tensor obs_full, torch::Tensor final_obs,
+                            torch::Tensor act_buf, torch::Tensor rew_buf,
+                            torch::Tensor done_buf) {
+  const int L = (int)weights.size();
+  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
+  TORCH_CHECK((int)biases.size() == L && (int)acts.size() == L,
+              "weights/biases/acts length mismatch");
+  CartPoleRolloutArgs a{};
+  a.N = check_cartpole_carry(state, elapsed);
+  check_f32_gpu(obs_full, "obs_full");
+  TORCH_CHECK(obs_full.dim() == 3 && obs_full.size(0) >= 2 &&
+                  obs_full.size(1) == a.N && obs_full.size(2) == 4,
+              "obs_full must be [steps+1, N, 4]");
+  a.steps = (int)obs_full.size(0) - 1;
+  const int64_t SN = (int64_t)a.steps * a.N;
+  check_out(final_obs, torch::kFloat32, SN * 4, "final_obs");
+  check_out(act_buf, torch::kInt64, SN, "act_buf");
+  check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
+  check_out(done_buf, torch::kUInt8, SN, "done_buf");
+  a.n_layers = L;
+  a.dims[0] = 4;
+  for (int l = 0; l < L; ++l) {
+    check_f32_gpu(weights[l], "weight");
+    check_f32_gpu(biases[l], "bias");
+    a.dims[l + 1] = (int)weights[l].size(0);
+    TORCH_CHECK(weights[l].dim() == 2 && (int)weights[l].size(1) == a.dims[l],
+                "weight shape mismatch");
+    TORCH_CHECK((int)biases[l].numel() == a.dims[l + 1], "bias shape mismatch");
+    TORCH_CHECK(a.dims[l + 1] >= 1 && a.dims[l + 1] <= ROLLOUT_MAX_WIDTH,
+                "cartpole_rollout_fused: layer width must be in [1, ",
+                ROLLOUT_MAX_WIDTH, "]");
+    a.w[l] = weights[l].data_ptr<float>();
+    a.b[l] = biases[l].data_ptr<float>();
+    a.acts[l] = (int)acts[l];
+  }
+  TORCH_CHECK(cartpole_rollout_fused_lds_bytes(a.dims, L) <= CARTPOLE_ROLLOUT_MAX_LDS,
+              "cartpole_rollout_fused: net image exceeds the LDS budget");
+  a.state = state.data_ptr<double>();
+  a.elapsed = elapsed.data_ptr<int>();
+  a.obs_full = obs_full.data_ptr<float>();
+  a.final_obs = final_obs.data_ptr<float>();
+  a.act_buf = reinterpret_cast<long long*>(act_buf.data_ptr<int64_t>());
+  a.rew_buf = rew_buf.data_ptr<float>();
+  a.done_buf = done_buf.data_ptr<uint8_t>();
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.max_steps = (int)max_steps;
+  a.start_with_reset = start_with_reset ? 1 : 0;
+  a.policy_seed = (uint64_t)policy_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_cartpole_rollout_fused(a, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("cartpole_rollout_fused", &cartpole_rollout_fused,
+        "whole-epoch CartPole rollout in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"),
+        py::arg("policy_seed"), py::arg("env_seed"), py::arg("max_steps"),
+        py::arg("start_with_reset"), py::arg("ctr"), py::arg("state"),
+        py::arg("elapsed"), py::arg("obs_full"), py::arg("final_obs"),
+        py::arg("act_buf"), py::arg("rew_buf"), py::arg("done_buf"));
+  m.def("cartpole_rollout_fused_lds_bytes", &cartpole_rollout_fused_lds_bytes_py,
+        "dynamic LDS of cartpole_rollout_fused for a net [4, ..., n_act]");
+  m.def("cartpole_rollout_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
+                                      CARTPOLE_ROLLOUT_MAX_LDS};
+        },
+        "(max layers, max width, LDS budget in bytes) of cartpole_rollout_fused");
+  m.def("cartpole_env_step", &cartpole_env_step,
+        "CartPole transition + termination + autoreset (gfx950)",
+        py::arg("state"), py::arg("elapsed"), py::arg("actions"),
+        py::arg("max_steps"), py::arg("seed"), py::arg("offset"),
+        py::arg("offset_ctr") = py::none(), py::arg("obs") = py::none(),
+        py::arg("final_obs") = py::none(), py::arg("reward") = py::none(),
+        py::arg("done") = py::none());
+  m.def("cartpole_env_reset", &cartpole_env_reset,
+        "CartPole init states (gfx950)", py::arg("state"), py::arg("elapsed"),
+        py::arg("seed"), py::arg("offset"), py::arg("offset_ctr") = py::none(),
+        py::arg("obs") = py::none());
   m.def("ppo_rollout_fused", &ppo_rollout_fused,
         "whole-epoch PPO rollout in one persistent kernel (gfx950)",
         py::arg("weights"), py::arg("biases"), py::arg("acts"),
@@ -1589,7 +1780,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("noise_scale"), py::arg("limit"),
         py::arg("offset_ctr") = py::none(), py::arg("out") = py::none());
   m.def("categorical_sample", &categorical_sample,
-        "Philox categorical action sample (gfx950)");
+        "Philox categorical action sample (gfx950)", py::arg("logits"),
+        py::arg("seed"), py::arg("offset"), py::arg("offset_ctr") = py::none(),
+        py::arg("out") = py::none());
   m.def("synthetic_env_step", &synthetic_env_step,
         "fused synthetic-env transition + reward (gfx950)", py::arg("state"),
         py::arg("actions"), py::arg("A"), py::arg("B"), py::arg("w"),

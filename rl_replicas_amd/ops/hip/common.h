@@ -236,6 +236,28 @@ struct RolloutFusedArgs {
   uint64_t policy_seed, env_seed;
 };
 
+// persistent CartPole rollout kernel (cartpole_rollout_kernels.hip): one
+// workgroup carries ROLLOUT_ROWS instances through all `steps` iterations
+// of forward -> categorical sample -> Euler step / termination / autoreset.
+struct CartPoleRolloutArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 4 (obs), dims[L] == n_act
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;
+  double* state;           // [N, 4] env carry (read unless start_with_reset)
+  int* elapsed;            // [N]    env carry
+  float* obs_full;         // [steps + 1, N, 4]
+  float* final_obs;        // [steps, N, 4] true successors
+  long long* act_buf;      // [steps, N]
+  float* rew_buf;          // [steps, N]
+  unsigned char* done_buf; // [steps, N]
+  const unsigned long long* ctr;  // device RNG counter (read once)
+  int N, steps, max_steps;
+  int start_with_reset;
+  uint64_t policy_seed, env_seed;
+};
+
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)
 struct ReplayGatherArgs {
   const float* obs;   // [cap, O] ring storage

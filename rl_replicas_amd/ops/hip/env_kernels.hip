@@ -10,6 +10,10 @@
 // reduction, and (on lockstep horizon boundaries) the autoreset init
 // state — N x O is a few thousand elements, so this regime is pure
 // launch-latency: fewer launches IS the optimization.
+//
+// CartPole-v1 (DeviceCartPoleEnv) has its own step/reset kernels below:
+// fp64 state, one thread per instance, per-instance termination,
+// truncation and autoreset.
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
@@ -48,6 +52,54 @@ __global__ __launch_bounds__(256) void synthetic_env_reset_kernel(
   if (offset_ptr) offset += *offset_ptr;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256)
     s_out[i] = 0.1f * philox_normal(seed, offset, (uint32_t)i);
+}
+
+// CartPole-v1 with per-instance termination and autoreset: one thread per
+// instance.  state fp64 [N,4] and elapsed int32 [N] are updated in place;
+// obs is the post-autoreset observation, final_obs the true successor.
+__global__ __launch_bounds__(256) void cartpole_env_step_kernel(
+    double* __restrict__ state, int* __restrict__ elapsed,
+    const int64_t* __restrict__ actions, float* __restrict__ obs,
+    float* __restrict__ final_obs, float* __restrict__ reward,
+    uint8_t* __restrict__ done, int N, int max_steps, uint64_t seed,
+    uint64_t offset, const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
+    double s[4];
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = state[(long)row * 4 + k];
+    int el = elapsed[row];
+    float fin[4], ob[4];
+    const bool d = cartpole_env_row(s, &el, (int)actions[row], max_steps, seed,
+                                    offset, (uint32_t)row, fin, ob);
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      state[(long)row * 4 + k] = s[k];
+      obs[(long)row * 4 + k] = ob[k];
+      final_obs[(long)row * 4 + k] = fin[k];
+    }
+    elapsed[row] = el;
+    reward[row] = 1.f;
+    done[row] = d ? 1 : 0;
+  }
+}
+
+// fresh CartPole states for all N instances
+__global__ __launch_bounds__(256) void cartpole_env_reset_kernel(
+    double* __restrict__ state, int* __restrict__ elapsed, float* __restrict__ obs,
+    int N, uint64_t seed, uint64_t offset,
+    const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
+    double s[4];
+    cartpole_reset_draw(seed, offset, (uint32_t)row, s);
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      state[(long)row * 4 + k] = s[k];
+      obs[(long)row * 4 + k] = (float)s[k];
+    }
+    elapsed[row] = 0;
+  }
 }
 
 // advance a device RNG counter (graph-replayable: one bump per epoch)

@@ -1,9 +1,10 @@
-// Per-row arithmetic of one rollout step, shared by the three stand-alone
+// Per-row arithmetic of one rollout step, shared by the stand-alone
 // kernels (fused_mlp_fwd_f32_t, gaussian_sample_kernel,
-// synthetic_env_step_kernel) and the persistent rollout kernel
-// (rollout_fused_kernels.hip).  Every caller inlines the SAME expressions
-// in the SAME order, so both routes produce the same bytes; the operands
-// may live in global memory or in LDS.
+// categorical_sample_kernel, synthetic_env_step_kernel,
+// cartpole_env_step_kernel) and the persistent rollout kernels
+// (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip).  Every caller
+// inlines the SAME expressions in the SAME order, so both routes produce
+// the same bytes; the operands may live in global memory or in LDS.
 #pragma once
 #include "common.h"
 #include "philox.h"
@@ -111,4 +112,88 @@ DEV_INLINE void synthetic_env_row(const float* s, const float* a, const float* A
   }
   *out_o_p = out_o;
   *s_next_p = s_next;
+}
+
+// one categorical action: inverse CDF over softmax(logits[0..n)) on the
+// uniform keyed by (seed, offset, row)
+DEV_INLINE int categorical_sample_row(const float* lg, int n, uint64_t seed,
+                                      uint64_t offset, uint32_t row) {
+  float m = lg[0];
+  for (int j = 1; j < n; ++j) m = fmaxf(m, lg[j]);
+  float z = 0.f;
+  for (int j = 0; j < n; ++j) z += __expf(lg[j] - m);
+  uint32_t r[4];
+  philox4(seed, offset, row, r);
+  const float u = u32_to_open_unit(r[0]) * z;
+  float acc = 0.f;
+  int pick = n - 1;
+  for (int j = 0; j < n; ++j) {
+    acc += __expf(lg[j] - m);
+    if (u <= acc) { pick = j; break; }
+  }
+  return pick;
+}
+
+// CartPole-v1 (envs/classic.py::CartPoleEnv._step_b): one Euler step of
+// s = (x, x_dot, theta, theta_dot) in fp64, the host env's constants and
+// expression order, no contraction.  Returns terminated.
+DEV_INLINE bool cartpole_row_step(double s[4], int action) {
+#pragma clang fp contract(off)
+  constexpr double GRAVITY = 9.8;
+  constexpr double MASSPOLE = 0.1;
+  constexpr double TOTAL_MASS = 1.0 + 0.1;
+  constexpr double LENGTH = 0.5;
+  constexpr double POLEMASS_LENGTH = 0.1 * 0.5;
+  constexpr double FORCE_MAG = 10.0;
+  constexpr double TAU = 0.02;
+  constexpr double THETA_THRESHOLD = 24.0 * 3.141592653589793 / 360.0;
+  constexpr double X_THRESHOLD = 2.4;
+  double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+  const double force = action == 1 ? FORCE_MAG : -FORCE_MAG;
+  const double costheta = cos(theta);
+  const double sintheta = sin(theta);
+  const double temp =
+      (force + POLEMASS_LENGTH * (theta_dot * theta_dot) * sintheta) / TOTAL_MASS;
+  const double thetaacc =
+      (GRAVITY * sintheta - costheta * temp) /
+      (LENGTH * (4.0 / 3.0 - MASSPOLE * (costheta * costheta) / TOTAL_MASS));
+  const double xacc = temp - POLEMASS_LENGTH * thetaacc * costheta / TOTAL_MASS;
+  x = x + TAU * x_dot;
+  x_dot = x_dot + TAU * xacc;
+  theta = theta + TAU * theta_dot;
+  theta_dot = theta_dot + TAU * thetaacc;
+  s[0] = x; s[1] = x_dot; s[2] = theta; s[3] = theta_dot;
+  return fabs(x) > X_THRESHOLD || fabs(theta) > THETA_THRESHOLD;
+}
+
+// CartPole init state: four uniforms strictly inside (-0.05, 0.05) from ONE
+// Philox call keyed by (seed, offset, row)
+DEV_INLINE void cartpole_reset_draw(uint64_t seed, uint64_t offset, uint32_t row,
+                                    double out[4]) {
+#pragma clang fp contract(off)
+  uint32_t r[4];
+  philox4(seed, offset, row, r);
+  #pragma unroll
+  for (int k = 0; k < 4; ++k)
+    out[k] = -0.05 + 0.1 * (((double)r[k] + 0.5) * (1.0 / 4294967296.0));
+}
+
+// one whole env row of VectorEnv.step semantics: Euler step, termination,
+// truncation (max_steps <= 0: none), autoreset.  s/elapsed are updated in
+// place to the next LIVE state; fin is the true successor observation,
+// obs the post-autoreset one.  Returns done.
+DEV_INLINE bool cartpole_env_row(double s[4], int* elapsed, int action,
+                                 int max_steps, uint64_t seed, uint64_t offset,
+                                 uint32_t row, float fin[4], float obs[4]) {
+  const bool terminated = cartpole_row_step(s, action);
+  const int el = *elapsed + 1;
+  const bool truncated = max_steps > 0 && el >= max_steps && !terminated;
+  const bool done = terminated || truncated;
+  #pragma unroll
+  for (int k = 0; k < 4; ++k) fin[k] = (float)s[k];
+  if (done) cartpole_reset_draw(seed, offset, row, s);
+  *elapsed = done ? 0 : el;
+  #pragma unroll
+  for (int k = 0; k < 4; ++k) obs[k] = (float)s[k];
+  return done;
 }

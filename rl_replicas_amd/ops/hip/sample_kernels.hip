@@ -30,24 +30,13 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(
 }
 
 // categorical sample: inverse-CDF over softmax(logits) per row
+// (offset_ptr: optional device counter, as in gaussian_sample_kernel)
 __global__ __launch_bounds__(256) void categorical_sample_kernel(
     const float* __restrict__ logits, int64_t* __restrict__ out, int B, int N,
-    uint64_t seed, uint64_t offset) {
-  for (int row = blockIdx.x * 256 + threadIdx.x; row < B; row += gridDim.x * 256) {
-    const float* lg = logits + (long)row * N;
-    float m = lg[0];
-    for (int j = 1; j < N; ++j) m = fmaxf(m, lg[j]);
-    float z = 0.f;
-    for (int j = 0; j < N; ++j) z += __expf(lg[j] - m);
-    uint32_t r[4];
-    philox4(seed, offset, (uint32_t)row, r);
-    const float u = u32_to_open_unit(r[0]) * z;
-    float acc = 0.f;
-    int pick = N - 1;
-    for (int j = 0; j < N; ++j) {
-      acc += __expf(lg[j] - m);
-      if (u <= acc) { pick = j; break; }
-    }
-    out[row] = pick;
-  }
+    uint64_t seed, uint64_t offset,
+    const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < B; row += gridDim.x * 256)
+    out[row] = categorical_sample_row(logits + (long)row * N, N, seed, offset,
+                                      (uint32_t)row);
 }

@@ -1,0 +1,339 @@
+"""The device CartPole rollout (gpu-marked): the stand-alone step / reset /
+sample kernels against the numpy env, and the persistent kernel
+cartpole_rollout_fused against the multi-kernel graph body with torch.equal
+(both inline the row code of rollout_steps.h and use the same Philox
+offsets, so no tolerance applies).
+
+N = 5 (less than one 16-row tile), 16 (exactly one), 37 (two tiles and a
+5-row tail).  Nets [4,64,32,2] and [4,7,2], whose hidden dim is no multiple
+of 4 or 16.  steps = 6 with horizon 4, so truncation falls inside the epoch.
+
+Staged rows (kind = row % 5) put every branch of the transition at a known
+place: terminate on x, terminate on theta, truncate only, terminate on the
+horizon step, continue."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+pytestmark = pytest.mark.gpu
+
+DEVICE = "cuda"
+NS = [5, 16, 37]
+NETS = {"bench": [4, 64, 32, 2], "awkward": [4, 7, 2]}
+STEPS = 6
+HORIZON = 4
+CTR_BASE = 1 << 40
+THETA_THRESHOLD = 12 * 2 * math.pi / 360
+X_THRESHOLD = 2.4
+
+
+def _staged(n, horizon):
+    """fp64 states [n,4], elapsed [n] and the expected done flag per row."""
+    kinds = np.arange(n) % 5
+    rows = np.array([
+        [2.39, 1.0, 0.0, 0.0],      # terminates on x
+        [0.0, 0.0, 0.205, 1.0],     # terminates on theta
+        [0.01, 0.0, 0.01, 0.0],     # only truncates
+        [2.39, 1.0, 0.0, 0.0],      # terminates on the horizon step
+        [0.01, 0.02, -0.01, 0.03],  # continues
+    ])
+    state = rows[kinds] + 1e-4 * np.arange(n)[:, None] * np.array([0.0, 1.0, 0.0, 1.0])
+    elapsed = np.where((kinds == 2) | (kinds == 3), horizon - 1, 0).astype(np.int32)
+    return state, elapsed, kinds != 4
+
+
+def _ulp_close(got32, want64):
+    want32 = want64.astype(np.float32)
+    return (np.abs(got32 - want32) <= np.spacing(np.abs(want32))).all()
+
+
+@pytest.mark.parametrize("n", NS)
+def test_step_kernel_matches_numpy(n):
+    from rl_replicas_amd.envs import CartPoleEnv, DeviceCartPoleEnv
+
+    state, elapsed, expect_done = _staged(n, HORIZON)
+    actions = np.random.default_rng(n).integers(0, 2, size=n)
+    ref = CartPoleEnv()
+    ref.state = state.copy()
+    _, _, terminated = ref._step_b(actions)
+    truncated = (elapsed + 1 >= HORIZON) & ~terminated
+    ref_done = terminated | truncated
+    # every oracle row is clear of both thresholds, so done must be equal
+    # everywhere and no row is excluded
+    assert (np.abs(np.abs(ref.state[:, 0]) - X_THRESHOLD) >= 1e-6).all()
+    assert (np.abs(np.abs(ref.state[:, 2]) - THETA_THRESHOLD) >= 1e-6).all()
+    assert np.array_equal(ref_done, expect_done)
+    kinds = np.arange(n) % 5
+    assert np.array_equal(terminated, (kinds == 0) | (kinds == 1) | (kinds == 3))
+
+    env = DeviceCartPoleEnv(n, device=DEVICE, max_episode_steps=HORIZON)
+    env.reset(seed=3)
+    env.state.copy_(torch.from_numpy(state))
+    env.elapsed.copy_(torch.from_numpy(elapsed))
+    obs, reward, done, final_obs = env.step(torch.from_numpy(actions).to(DEVICE))
+    torch.cuda.synchronize()
+    done = done.cpu().numpy()
+    new_state = env.state.cpu().numpy()
+    new_elapsed = env.elapsed.cpu().numpy()
+    obs, final_obs = obs.cpu().numpy(), final_obs.cpu().numpy()
+    live = ~ref_done
+    diff = np.abs(new_state[live] - ref.state[live]).max() if live.any() else 0.0
+    print(f"n={n}: max abs state difference on live rows {diff:.3e}")
+    assert done.dtype == bool and np.array_equal(done, ref_done)
+    assert diff <= 1e-12
+    assert _ulp_close(obs[live], new_state[live])
+    assert np.array_equal(new_elapsed[live], elapsed[live] + 1)
+    assert _ulp_close(final_obs, ref.state)
+    assert (np.abs(new_state[ref_done]) < 0.05).all()
+    assert _ulp_close(obs[ref_done], new_state[ref_done])
+    assert (new_elapsed[ref_done] == 0).all()
+    assert torch.equal(reward.cpu(), torch.ones(n))
+
+
+def test_reset_kernel_draws():
+    from rl_replicas_amd.envs import DeviceCartPoleEnv
+
+    n = 4096
+    env = DeviceCartPoleEnv(n, device=DEVICE)
+    env.elapsed.fill_(7)
+    obs = env.reset(seed=11)
+    a = env.state.cpu().numpy().copy()
+    assert a.dtype == np.float64
+    assert (np.abs(a) < 0.05).all()
+    assert (env.elapsed == 0).all()
+    assert np.array_equal(obs.cpu().numpy(), a.astype(np.float32))
+    assert len(np.unique(a)) > 0.999 * a.size  # rows and components differ
+    assert (a[0] != a[1]).all()
+    env.reset()
+    b = env.state.cpu().numpy()
+    assert (a != b).mean() > 0.999  # the next offset is another draw
+    env.reset(seed=11)
+    assert np.array_equal(env.state.cpu().numpy(), a)
+    draws = a.reshape(-1)
+    bound = 5 * (0.1 / math.sqrt(12)) / math.sqrt(draws.size)
+    print(f"mean of {draws.size} draws {draws.mean():.3e}, bound {bound:.3e}")
+    assert abs(draws.mean()) <= bound
+
+
+def test_categorical_sample_counter_and_out():
+    from rl_replicas_amd import ops
+
+    ext = ops._load_extension()
+    logits = torch.randn(37, 7, device=DEVICE)
+    c = torch.tensor([12345], dtype=torch.int64, device=DEVICE)
+    buf = torch.full((37,), -1, dtype=torch.int64, device=DEVICE)
+    got = ext.categorical_sample(logits, 99, 3, offset_ctr=c, out=buf)
+    want = ext.categorical_sample(logits, 99, 3 + 12345)
+    assert got.data_ptr() == buf.data_ptr()
+    assert torch.equal(buf, want)
+    assert not torch.equal(want, ext.categorical_sample(logits, 99, 3))
+    assert int(c.item()) == 12345
+
+
+def _policy(dims):
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.policies import CategoricalPolicy
+
+    pnet = MLP(dims).to(DEVICE)
+    return pnet, CategoricalPolicy(pnet, ops.make_adam(pnet.parameters(), lr=3e-4))
+
+
+def _rollouts(monkeypatch, fused, dims, n_envs, continuous, epochs=3,
+              stage_before=None, mutate_before=None):
+    """Run `epochs` sampler calls; per call a dict of the graph and clones
+    of its buffers, the env carry and the counter."""
+    from rl_replicas_amd.envs import DeviceCartPoleEnv
+    from rl_replicas_amd.samplers import DeviceEpisodicSampler
+
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1" if fused else "0")
+    torch.manual_seed(77)
+    env = DeviceCartPoleEnv(n_envs, device=DEVICE, max_episode_steps=HORIZON)
+    pnet, policy = _policy(dims)
+    sampler = DeviceEpisodicSampler(env, seed=5, is_continuous=continuous)
+    out = []
+    for e in range(epochs):
+        if stage_before == e:
+            state, elapsed, _ = _staged(n_envs, HORIZON)
+            env.state.copy_(torch.from_numpy(state))
+            env.elapsed.copy_(torch.from_numpy(elapsed))
+        if mutate_before == e:
+            with torch.no_grad():  # every action becomes 0
+                list(pnet.parameters())[-1].copy_(torch.tensor([20.0, -20.0]))
+        exp = sampler.sample(n_envs * STEPS, policy)
+        g = sampler._graphs[(STEPS, e == 0 or not continuous)]
+        torch.cuda.synchronize()
+        out.append({
+            "g": g, "exp": exp,
+            "obs_full": g.obs_full.clone(), "final_obs": g.final_obs.clone(),
+            "act_buf": g.act_buf.clone(), "rew_buf": g.rew_buf.clone(),
+            "done_buf": g.done_buf.clone(), "state": env.state.clone(),
+            "elapsed": env.elapsed.clone(), "ctr": int(sampler._graph_ctr.item()),
+        })
+    return out
+
+
+KEYS = ("obs_full", "final_obs", "act_buf", "rew_buf", "done_buf", "state", "elapsed")
+
+
+def _assert_same(f_run, p_run):
+    for e, (f, p) in enumerate(zip(f_run, p_run)):
+        assert f["g"].fused and not p["g"].fused
+        assert f["ctr"] == p["ctr"] == CTR_BASE + (e + 1) * (STEPS + 1)
+        for k in KEYS:
+            assert torch.equal(f[k], p[k]), f"{k} differs in epoch {e}"
+
+
+def _assert_invariants(r, n_envs):
+    obs_full, final_obs = r["obs_full"], r["final_obs"]
+    done = r["done_buf"].bool()
+    assert torch.isfinite(obs_full).all() and torch.isfinite(final_obs).all()
+    assert torch.isfinite(r["state"]).all()
+    nxt = obs_full[1:]
+    assert torch.equal(nxt[~done], final_obs[~done])
+    assert (nxt[done].abs() < 0.05).all()
+    assert torch.equal(r["rew_buf"], torch.ones(STEPS, n_envs, device=DEVICE))
+    assert ((r["act_buf"] == 0) | (r["act_buf"] == 1)).all()
+    assert torch.equal(obs_full[STEPS], r["state"].float())
+    assert r["done_buf"].dtype == torch.uint8 and r["act_buf"].dtype == torch.int64
+
+
+@pytest.mark.parametrize("continuous", [False, True], ids=["reset", "carry"])
+@pytest.mark.parametrize("net", list(NETS))
+@pytest.mark.parametrize("n_envs", NS)
+def test_fused_equals_multi_kernel_body(monkeypatch, n_envs, net, continuous):
+    """Three consecutive replays: every buffer, the env carry and the RNG
+    counter are equal; the exact invariants hold on the graphed outputs."""
+    stage = 1 if continuous else None
+    f = _rollouts(monkeypatch, True, NETS[net], n_envs, continuous, stage_before=stage)
+    p = _rollouts(monkeypatch, False, NETS[net], n_envs, continuous, stage_before=stage)
+    _assert_same(f, p)
+    for r in f:
+        _assert_invariants(r, n_envs)
+    # the replays draw fresh randomness
+    assert not torch.equal(f[0]["obs_full"], f[2]["obs_full"])
+    for e in (1, 2):
+        assert f[e]["g"].start_with_reset == (not continuous)
+    if continuous:
+        # staged rows are done at step 0 exactly where expected
+        _, _, expect_done = _staged(n_envs, HORIZON)
+        assert f[1]["done_buf"][0].cpu().numpy().astype(bool).tolist() == expect_done.tolist()
+        state, _, _ = _staged(n_envs, HORIZON)
+        assert torch.equal(f[1]["obs_full"][0].cpu(), torch.from_numpy(state).float())
+        # the third epoch starts from the second's carry
+        assert torch.equal(f[2]["obs_full"][0], f[1]["state"].float())
+    else:
+        # horizon 4 from a reset: every instance is done by step 3, and
+        # truncated exactly there unless it terminated earlier
+        done = f[0]["done_buf"].bool()
+        assert done[:HORIZON].any(dim=0).all()
+        no_early = ~done[: HORIZON - 1].any(dim=0)
+        assert done[HORIZON - 1][no_early].all()
+
+
+def test_identically_seeded_runs_are_bit_equal(monkeypatch):
+    a = _rollouts(monkeypatch, True, NETS["bench"], 37, True, stage_before=1)
+    b = _rollouts(monkeypatch, True, NETS["bench"], 37, True, stage_before=1)
+    for ra, rb in zip(a, b):
+        assert ra["ctr"] == rb["ctr"]
+        for k in KEYS:
+            assert torch.equal(ra[k], rb[k])
+        fa, fb = ra["exp"].to_flat_batch(), rb["exp"].to_flat_batch()
+        for k in fa:
+            assert torch.equal(fa[k], fb[k]), k
+
+
+@pytest.mark.parametrize("continuous", [False, True], ids=["reset", "carry"])
+def test_weights_are_read_by_pointer(monkeypatch, continuous):
+    """Parameters changed in place between replays: both routes see the
+    change (every action becomes 0) and stay equal."""
+    f = _rollouts(monkeypatch, True, NETS["bench"], 37, continuous, mutate_before=1)
+    p = _rollouts(monkeypatch, False, NETS["bench"], 37, continuous, mutate_before=1)
+    _assert_same(f, p)
+    assert f[0]["act_buf"].any()
+    assert not f[1]["act_buf"].any() and not f[2]["act_buf"].any()
+
+
+def test_flat_cache_matches_graph_buffers(monkeypatch):
+    (r,) = _rollouts(monkeypatch, True, NETS["bench"], 37, False, epochs=1)
+    flat = r["exp"].to_flat_batch()
+    n = 37
+    assert torch.equal(flat["observations"].view(n, STEPS, 4),
+                       r["obs_full"][:STEPS].transpose(0, 1))
+    assert flat["actions"].dtype == torch.int64 and flat["actions"].shape == (n * STEPS,)
+    assert torch.equal(flat["actions"].view(n, STEPS), r["act_buf"].t())
+    done = r["done_buf"].t().bool()
+    assert torch.equal(flat["step_dones"].view(n, STEPS).bool(), done)
+    ends = done.clone()
+    ends[:, -1] = True
+    offsets = flat["episode_offsets"].cpu()
+    assert torch.equal(offsets[1:].long() - 1, torch.nonzero(ends.reshape(-1).cpu()).view(-1))
+    assert torch.equal(flat["episode_dones"].cpu(), done.reshape(-1).cpu()[offsets[1:].long() - 1])
+    assert sum(r["exp"].episode_lengths) == n * STEPS
+    assert r["exp"].episode_returns == [float(L) for L in r["exp"].episode_lengths]
+    # bootstrap rows: final_obs on done episodes, the live obs on cuts
+    fin = r["final_obs"].transpose(0, 1).reshape(n * STEPS, 4)
+    last = flat["last_observations"]
+    for e, end in enumerate((offsets[1:].long() - 1).tolist()):
+        want = fin[end] if bool(flat["episode_dones"][e]) else r["obs_full"][STEPS, end // STEPS]
+        assert torch.equal(last[e], want)
+
+
+def test_gate(monkeypatch):
+    from rl_replicas_amd import envs, ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.ops import fused_rollout
+    from rl_replicas_amd.policies import GaussianPolicy
+
+    (r,) = _rollouts(monkeypatch, True, [4, 128, 2], 16, False, epochs=1)
+    assert not r["g"].fused  # outside the tile limit: the multi-kernel body
+    _assert_invariants(r, 16)
+
+    cenv = envs.DeviceCartPoleEnv(8, device=DEVICE)
+    _, cat = _policy([4, 16, 2])
+    assert fused_rollout.cartpole_supported(cat, cenv)
+    assert fused_rollout.cartpole_fused_eligible(cat, cenv)
+    assert not fused_rollout.cartpole_supported(cat, envs.DeviceCartPoleEnv(8, device="cpu"))
+    gnet = MLP([4, 16, 2]).to(DEVICE)
+    log_std = nn.Parameter(-0.5 * torch.ones(2, device=DEVICE))
+    gauss = GaussianPolicy(gnet, ops.make_adam(list(gnet.parameters()) + [log_std], lr=3e-4),
+                           log_std)
+    assert not fused_rollout.cartpole_supported(gauss, cenv)
+    denv = envs.DeviceVectorEnv("HalfCheetah-v4", num_envs=8, device=DEVICE)
+    assert not fused_rollout.cartpole_supported(cat, denv)
+    assert not fused_rollout.supported(cat, cenv)  # the lockstep gate is unchanged
+
+
+def test_ppo_end_to_end(monkeypatch, tmp_path):
+    """PPO + CategoricalPolicy + DeviceEpisodicSampler, two epochs at N=16,
+    steps=32: parameters stay finite; two identically seeded runs end with
+    bit-equal parameters."""
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.algorithms import PPO
+    from rl_replicas_amd.envs import DeviceCartPoleEnv
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.samplers import DeviceEpisodicSampler
+    from rl_replicas_amd.value_function import ValueFunction
+
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+
+    def run(d):
+        torch.manual_seed(21)
+        env = DeviceCartPoleEnv(16, device=DEVICE)
+        pnet, policy = _policy([4, 64, 64, 2])
+        vnet = MLP([4, 64, 64, 1]).to(DEVICE)
+        vf = ValueFunction(vnet, ops.make_adam(vnet.parameters(), lr=1e-3))
+        sampler = DeviceEpisodicSampler(env, seed=3, is_continuous=True)
+        model = PPO(policy, vf, env, sampler, num_policy_gradients=2, num_value_gradients=2)
+        model.learn(num_epochs=2, batch_size=16 * 32, output_dir=str(d))
+        torch.cuda.synchronize()
+        assert sampler._graphs and all(g.fused for g in sampler._graphs.values())
+        return [p.detach().clone() for p in list(pnet.parameters()) + list(vnet.parameters())]
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    for pa, pb in zip(a, b):
+        assert torch.isfinite(pa).all()
+        assert torch.equal(pa, pb)
