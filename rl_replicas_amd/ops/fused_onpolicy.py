@@ -781,7 +781,10 @@ def ppo_twin_eligible(algo, obs: Tensor) -> bool:
     and the fp32 narrow in-kernel-forward value iteration are both
     eligible, both optimizers are FusedAdam, graphs are on, the loops
     capture whole (no per-iteration collectives) and P <= V.
-    RL_REPLICAS_AMD_PPO_TWIN=0 selects the separate loops."""
+    RL_REPLICAS_AMD_PPO_TWIN=0 selects the separate loops.
+    RL_REPLICAS_AMD_TWIN_SHAPED=0 keeps the twin launch on the generic
+    kernel where the [in, 64, 32, out] shaped one would run (the
+    extension reads it per call; a captured graph keeps its kernel)."""
     import os
 
     if os.environ.get("RL_REPLICAS_AMD_PPO_TWIN", "1") == "0":

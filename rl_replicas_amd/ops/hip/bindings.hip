@@ -39,6 +39,9 @@ void launch_mlp_grad_reduce_adam(const ReduceAdamArgs& a, long grand,
                                  hipStream_t stream);
 void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
                                int n_blocks, int rows, hipStream_t stream);
+void launch_mlp_bwd_fused_twin_shaped(const MLPBwdTwinArgs& a, int n_blocks,
+                                      hipStream_t stream);
+size_t mlp_bwd_fused_shaped_lds(int in_d);
 bool mlp_reduce_adam_is_staged(int n_blocks, long grand);
 void launch_mlp_grad_reduce_adam_twin(const ReduceAdamArgs& pol, long grand_pol,
                                       const ReduceAdamArgs& val, long grand_val,
@@ -976,7 +979,8 @@ torch::Tensor value_loss_finalize(torch::Tensor partials, int64_t fb) {
   const int stride = (int)partials.size(1);
   TORCH_CHECK((int)fb <= stride, "fb exceeds partials row stride");
   auto scalars = torch::empty({rows}, partials.options());
-  hipLaunchKernelGGL(value_loss_finalize_rows, dim3((rows + 255) / 256),
+  // one wave per row, four rows per workgroup
+  hipLaunchKernelGGL(value_loss_finalize_rows, dim3((rows + 3) / 4),
                      dim3(256), 0, current_stream(),
                      partials.data_ptr<float>(), scalars.data_ptr<float>(),
                      rows, (int)fb, stride);
@@ -1397,6 +1401,31 @@ torch::Tensor gaussian_ppo_policy_iter(
   return torch::empty({0}, x.options());  // dx slot: never computed here
 }
 
+// The shape-specialised twin kernel (mlp_bwd_fused_twin_shaped_f32) covers
+// 3-layer nets [in <= 64, 64, 32, out <= 16] on 32-row blocks; the value
+// half has out == 1.  dims = [in, hidden..., out] of each net.
+// RL_REPLICAS_AMD_TWIN_SHAPED=0 forces the generic twin kernel; the switch
+// is read per call (a captured graph keeps what it was captured with).
+static bool twin_shaped_net_ok(const std::vector<int64_t>& d, int64_t max_out) {
+  return d.size() == 4 && d[0] >= 1 && d[0] <= 64 && d[1] == 64 &&
+         d[2] == 32 && d[3] >= 1 && d[3] <= max_out;
+}
+
+bool ppo_twin_uses_shaped(std::vector<int64_t> p_dims,
+                          std::vector<int64_t> v_dims, int64_t batch) {
+  const char* e = getenv("RL_REPLICAS_AMD_TWIN_SHAPED");
+  if (e != nullptr && e[0] == '0' && e[1] == '\0') return false;
+  return bwd_fused_rows((int)batch) == 32 && twin_shaped_net_ok(p_dims, 16) &&
+         twin_shaped_net_ok(v_dims, 1) && p_dims[0] == v_dims[0];
+}
+
+static std::vector<int64_t> net_dims(const torch::Tensor& x,
+                                     const std::vector<torch::Tensor>& weights) {
+  std::vector<int64_t> d{x.size(1)};
+  for (const torch::Tensor& w : weights) d.push_back(w.size(0));
+  return d;
+}
+
 // Policy iteration i and value iteration i of one PPO epoch in the SAME
 // two launches (the two loops are independent: neither reads what the
 // other writes):
@@ -1459,8 +1488,15 @@ void gaussian_ppo_value_twin_iter(
   ta.val_loss_partials = v_partials_out.data_ptr<float>();
   ta.x = x.data_ptr<float>();
   auto stream = current_stream();
-  launch_mlp_bwd_fused_twin(ta, std::max(pb.fused_lds, v_lds), pb.fb, pb.brows,
-                            stream);
+  if (ppo_twin_uses_shaped(net_dims(x, weights), net_dims(x, v_weights),
+                           x.size(0))) {
+    TORCH_CHECK(mlp_bwd_fused_shaped_lds((int)x.size(1)) <= 80 * 1024,
+                "shaped twin kernel over its LDS budget");
+    launch_mlp_bwd_fused_twin_shaped(ta, pb.fb, stream);
+  } else {
+    launch_mlp_bwd_fused_twin(ta, std::max(pb.fused_lds, v_lds), pb.fb,
+                              pb.brows, stream);
+  }
   HIP_OK(hipGetLastError());
 
   const ReduceAdamArgs vra = fill_reduce_adam(
@@ -1739,6 +1775,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one 2-kernel Gaussian-PPO policy iteration (gfx950)");
   m.def("gaussian_ppo_value_twin_iter", &gaussian_ppo_value_twin_iter,
         "PPO policy + value iteration in one twin kernel pair (gfx950)");
+  m.def("ppo_twin_uses_shaped", &ppo_twin_uses_shaped,
+        "whether the twin iteration takes the [*,64,32,*] shaped kernel");
   m.def("reduce_adam_is_staged",
         [](int64_t n_blocks, int64_t grand) {
           return mlp_reduce_adam_is_staged((int)n_blocks, (long)grand);

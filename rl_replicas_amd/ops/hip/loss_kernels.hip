@@ -211,18 +211,26 @@ __global__ void loss_partials_finalize(const float* __restrict__ partials,
   else scalars[0] = s;
 }
 
-// batched row finalize for the captured value loop: one thread per row,
-// SAME serial summation order as loss_partials_finalize -> a deferred
-// finalize is bitwise-identical to 80 per-iteration launches.
-__global__ void value_loss_finalize_rows(const float* __restrict__ partials,
-                                         float* __restrict__ scalars, int rows,
-                                         int fb, int row_stride) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= rows) return;
+// batched row finalize for the captured value loop: one wave per row.  The
+// wave loads 64 partials per coalesced access and every lane then adds them
+// lane by lane (v_readlane), in the SAME serial order from 0.f as
+// loss_partials_finalize -> a deferred finalize is bitwise-identical to 80
+// per-iteration launches.  Grid: ceil(rows / 4) workgroups of 256.
+__global__ __launch_bounds__(256) void value_loss_finalize_rows(
+    const float* __restrict__ partials, float* __restrict__ scalars, int rows,
+    int fb, int row_stride) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;  // wave-uniform
   const float* row = partials + (long)r * row_stride;
   float s = 0.f;
-  for (int p = 0; p < fb; ++p) s += row[p];
-  scalars[r] = s;
+  for (int p0 = 0; p0 < fb; p0 += 64) {
+    const int v = p0 + lane < fb ? __float_as_int(row[p0 + lane]) : 0;
+    const int n = min(64, fb - p0);  // pads are never added
+    for (int p = 0; p < n; ++p)
+      s += __int_as_float(__builtin_amdgcn_readlane(v, p));
+  }
+  if (lane == 0) scalars[r] = s;
 }
 
 // logp only (old-policy snapshot at epoch start)

@@ -677,6 +677,506 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_twin_f32(MLPBwdTwinArgs a) 
 }
 
 // ---------------------------------------------------------------------------
+// shape-specialised twin iteration: 3-layer fp32 nets [in, H1, H2, out]
+// with compile-time hidden widths (in <= 64 and out <= 16 stay runtime,
+// wave-uniform trip counts).  Same arithmetic as mlp_bwd_fused_body<ROWS,
+// false, true, false> — every MFMA accumulator sees the same operand
+// values in the same k order, the seeds and the bias sums are the same
+// expressions — so results are bitwise those of the generic body.  What
+// changes is the schedule:
+//   * every global load (all three weight matrices, biases, the x tile,
+//     the per-row seed inputs) is issued at the top, before the first wait;
+//   * the MFMA loops carry no per-lane predicate: the x tile, the head dZ
+//     tile and the W images are zero-filled out to the padded k range, so a
+//     padded k-step multiplies 0.0f by 0.0f exactly as the masked one did;
+//   * a tile's LDS operands are all read ahead of its MFMA chain.
+// LDS (floats): five [ROWS][68] tiles (dZ ping-pong, x, h0, h1), the head
+// output [ROWS][20], the seed scratch, then the W images with row strides
+// = 2 mod 32 (a 16-row x 2-k half-wave read then covers 32 distinct banks).
+// ---------------------------------------------------------------------------
+#define SHAPED_TS 68   // activation / dZ tile row stride
+#define SHAPED_OS 20   // head-output tile row stride (out <= 16)
+#define SHAPED_AS 17   // staged actions row stride
+#define SHAPED_MAX_OUT 16
+
+template <int ROWS, int H1, int H2>
+struct ShapedLds {
+  static constexpr int W1S = H1 + 2;
+  static constexpr int W2S = H2 + 2;
+  static constexpr int DZA = 0;
+  static constexpr int DZB = DZA + ROWS * SHAPED_TS;
+  static constexpr int XT = DZB + ROWS * SHAPED_TS;
+  static constexpr int HID0 = XT + ROWS * SHAPED_TS;
+  static constexpr int HID1 = HID0 + ROWS * SHAPED_TS;
+  static constexpr int OUT = HID1 + ROWS * SHAPED_TS;
+  static constexpr int CBUF = OUT + ROWS * SHAPED_OS;  // c / loss / kl per row
+  static constexpr int LRED = CBUF + 3 * ROWS;
+  static constexpr int ACT = LRED + 4;
+  static constexpr int LSTD = ACT + ROWS * SHAPED_AS;
+  static constexpr int W1 = LSTD + SHAPED_MAX_OUT;
+  static constexpr int W2 = W1 + H2 * W1S;
+  static constexpr int W0 = W2 + SHAPED_MAX_OUT * W2S;  // [H1][w0 stride], last
+};
+
+// W0 image row stride: >= roundup4(in) columns, = 2 mod 32
+__host__ __device__ inline int shaped_w0_stride(int in_d) {
+  return ((in_d + 3) & ~3) <= 32 ? 34 : 66;
+}
+
+size_t mlp_bwd_fused_shaped_lds(int in_d) {
+  return (size_t)(ShapedLds<32, 64, 32>::W0 + 64 * shaped_w0_stride(in_d)) * 4;
+}
+
+// One MFMA chain of NK k-steps.  All
+// LDS operands are read first (the scheduling barrier keeps the compiler
+// from sinking the reads back between the MFMAs), so the chain pays one
+// LDS latency and then counted waits.  ap/bp point at this lane's operand
+// of k-step 0; astep/bstep are the float strides between k-steps.
+template <int NK>
+DEV_INLINE f32x4 shaped_chain1(const float* ap, int astep, const float* bp,
+                               int bstep) {
+  float a[NK], b[NK];
+  #pragma unroll
+  for (int s = 0; s < NK; ++s) {
+    a[s] = ap[s * astep];
+    b[s] = bp[s * bstep];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  #pragma unroll
+  for (int s = 0; s < NK; ++s)
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b[s], acc, 0, 0, 0);
+  return acc;
+}
+
+// Two output tiles of one wave, one chain after the other.  (Interleaving
+// the two chains' MFMAs behind one joint read phase was traced 0.3 us per
+// launch slower at the bench shape and is not kept.)
+template <int NK>
+DEV_INLINE void shaped_chain2(const float* ap0, const float* ap1, int astep,
+                              const float* bp0, const float* bp1, int bstep,
+                              f32x4& acc0, f32x4& acc1) {
+  acc0 = shaped_chain1<NK>(ap0, astep, bp0, bstep);
+  __builtin_amdgcn_sched_barrier(0);
+  acc1 = shaped_chain1<NK>(ap1, astep, bp1, bstep);
+}
+
+// bias partial of one layer: column c goes to thread 255 - c (as in the
+// generic body), summed over the rows in serial order
+template <int ROWS>
+DEV_INLINE void shaped_bias_partial(const float* dz, int out_d, int tid,
+                                    float* dst, const long WSN) {
+  const int c = 255 - tid;
+  if (c < out_d) {
+    float s = 0.f;
+    #pragma unroll
+    for (int r = 0; r < ROWS; ++r) s += dz[r * SHAPED_TS + c];
+    dst[(long)c * WSN] = s;
+  }
+}
+
+template <int ROWS, int H1, int H2, bool GAUSS>
+DEV_INLINE void mlp_bwd_fused_shaped_body(
+    const MLPBwdArgs& args, const float* __restrict__ x,
+    float* __restrict__ workspace, const float* __restrict__ mse_returns,
+    float* __restrict__ loss_partials, const GaussSeedArgs& gargs, float* smem,
+    const int bx, const long WSN) {
+  static_assert(ROWS == 32 && H1 == 64 && H2 == 32,
+                "wave -> tile maps below assume the <32, 64, 32> shape");
+  using LY = ShapedLds<ROWS, H1, H2>;
+  constexpr int TS = SHAPED_TS, OS = SHAPED_OS, AS = SHAPED_AS;
+  constexpr int W1S = LY::W1S, W2S = LY::W2S;
+  float* const dza = smem + LY::DZA;
+  float* const dzb = smem + LY::DZB;
+  float* const xt = smem + LY::XT;
+  float* const h0 = smem + LY::HID0;
+  float* const h1 = smem + LY::HID1;
+  float* const h2 = smem + LY::OUT;
+  float* const cbuf = smem + LY::CBUF;
+  float* const lbuf = cbuf + ROWS;
+  float* const kbuf = lbuf + ROWS;
+  float* const lred = smem + LY::LRED;
+  float* const actl = smem + LY::ACT;
+  float* const lsl = smem + LY::LSTD;
+  float* const w1l = smem + LY::W1;
+  float* const w2l = smem + LY::W2;
+  float* const w0l = smem + LY::W0;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int i = lane & 15;
+  const int k = lane >> 4;
+  const int row0 = bx * ROWS;
+  const int wr0 = (wave & 1) * 16;   // this wave's row tile (fwd / dgrad)
+  const int jt0 = (wave >> 1) * 16;  // and its first column tile
+  const int batch = args.batch;
+  const int in_d = args.dims[0];
+  const int D = args.dims[3];
+  const int in4 = (in_d + 3) & ~3;
+  const int in16 = (in_d + 15) & ~15;
+  const int w0s = shaped_w0_stride(in_d);
+  const int act0 = args.acts[0], act1 = args.acts[1], act2 = args.acts[2];
+  float* wsp = workspace + bx;  // element-major: ws[elem][block]
+
+  // ---- every global load of the launch, issued back to back ----
+  // W0 and the x tile are both [*, in_d] row-major and this block's x rows
+  // are contiguous, so flat element idx = tid + 256 u serves both.
+  const int n_w0 = H1 * in_d;
+  const int n_x = ROWS * in_d;
+  const int n_xv = min(ROWS, batch - row0) * in_d;  // rows >= batch read 0
+  const float* const xg = x + (long)row0 * in_d;
+  float gw0[16], gx[8], gw1[8], gw2[2];
+  #pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int idx = tid + 256 * u;
+    gw0[u] = idx < n_w0 ? args.w[0][idx] : 0.f;
+  }
+  #pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int idx = tid + 256 * u;
+    gx[u] = idx < n_xv ? xg[idx] : 0.f;
+  }
+  #pragma unroll
+  for (int u = 0; u < 8; ++u) gw1[u] = args.w[1][tid + 256 * u];  // H2*H1 = 2048
+  #pragma unroll
+  for (int u = 0; u < 2; ++u) {  // image rows >= D are zero
+    const int idx = tid + 256 * u;
+    gw2[u] = idx < D * H2 ? args.w[2][idx] : 0.f;
+  }
+  const float b0a = args.b[0][jt0 + i];
+  const float b0b = args.b[0][jt0 + 32 + i];
+  const float b1v = args.b[1][jt0 + i];
+  const float b2v = i < D ? args.b[2][i] : 0.f;
+  // seed inputs: thread tid < ROWS owns row tid; thread (ar, ad) owns
+  // elements (ar, ad) and (ar + 16, ad) of the [ROWS][16] head tiles
+  const int ar = tid >> 4, ad = tid & 15;
+  float olp = 0.f, advv = 0.f, retv = 0.f, ga0 = 0.f, ga1 = 0.f, lsv = 0.f;
+  if constexpr (GAUSS) {
+    if (tid < ROWS && row0 + tid < batch) {
+      olp = gargs.old_logp[row0 + tid];
+      advv = gargs.adv[row0 + tid];
+    }
+    if (ad < D) {
+      if (row0 + ar < batch) ga0 = gargs.actions[(long)(row0 + ar) * D + ad];
+      if (row0 + ar + 16 < batch)
+        ga1 = gargs.actions[(long)(row0 + ar + 16) * D + ad];
+    }
+    if (tid < D) lsv = gargs.log_std[tid];
+  } else {
+    if (tid < ROWS && row0 + tid < batch) retv = mse_returns[row0 + tid];
+  }
+  // gate-frozen PPO iteration: a no-op by definition (see the generic body)
+  if (GAUSS && gargs.skip_gate != nullptr && *gargs.skip_gate == 0.f) return;
+
+  // ---- stage to LDS ----
+  {
+    // (r, c) of idx = tid, then stepped by 256 elements without dividing
+    int r = tid / in_d, c = tid - r * in_d;
+    const int qs = 256 / in_d, rs = 256 - qs * in_d;
+    #pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int idx = tid + 256 * u;
+      if (idx < n_w0) w0l[r * w0s + c] = gw0[u];
+      if (u < 8 && idx < n_x) xt[r * TS + c] = gx[u < 8 ? u : 0];
+      c += rs;
+      r += qs;
+      if (c >= in_d) {
+        c -= in_d;
+        ++r;
+      }
+    }
+    // zero pads: W0 columns [in_d, in4) and x columns [in_d, in16)
+    if (tid < H1) {
+      for (int cc = in_d; cc < in4; ++cc) w0l[tid * w0s + cc] = 0.f;
+    } else if (tid < H1 + 4 * ROWS) {
+      const int rr = (tid - H1) >> 2;
+      for (int cc = in_d + ((tid - H1) & 3); cc < in16; cc += 4)
+        xt[rr * TS + cc] = 0.f;
+    }
+    #pragma unroll
+    for (int u = 0; u < 8; ++u)
+      w1l[((tid >> 6) + 4 * u) * W1S + (tid & 63)] = gw1[u];
+    #pragma unroll
+    for (int u = 0; u < 2; ++u)
+      w2l[((tid >> 5) + 8 * u) * W2S + (tid & 31)] = gw2[u];
+    if constexpr (GAUSS) {
+      actl[ar * AS + ad] = ga0;
+      actl[(ar + 16) * AS + ad] = ga1;
+      if (tid < SHAPED_MAX_OUT) lsl[tid] = lsv;
+    }
+  }
+  __syncthreads();
+
+  // ---- forward layer 0: two column tiles per wave ----
+  {
+    const int nk = in4 >> 2;
+    const float* ap = xt + (wr0 + i) * TS + k;
+    const float* bp0 = w0l + (jt0 + i) * w0s + k;
+    const float* bp1 = bp0 + 32 * w0s;
+    f32x4 acc0, acc1;
+    // wave-uniform dispatch on the k-step count: straight-line chains
+#define SHAPED_FWD0(N) \
+  case N: shaped_chain2<N>(ap, ap, 4, bp0, bp1, 4, acc0, acc1); break;
+    switch (nk) {
+      SHAPED_FWD0(1) SHAPED_FWD0(2) SHAPED_FWD0(3) SHAPED_FWD0(4)
+      SHAPED_FWD0(5) SHAPED_FWD0(6) SHAPED_FWD0(7) SHAPED_FWD0(8)
+      SHAPED_FWD0(9) SHAPED_FWD0(10) SHAPED_FWD0(11) SHAPED_FWD0(12)
+      SHAPED_FWD0(13) SHAPED_FWD0(14) SHAPED_FWD0(15)
+      default: shaped_chain2<16>(ap, ap, 4, bp0, bp1, 4, acc0, acc1); break;
+    }
+#undef SHAPED_FWD0
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = wr0 + k * 4 + r;
+      h0[rr * TS + jt0 + i] = act_apply(act0, acc0[r] + b0a);
+      h0[rr * TS + jt0 + 32 + i] = act_apply(act0, acc1[r] + b0b);
+    }
+  }
+  __syncthreads();
+  // ---- forward layer 1: one tile per wave, K = H1 ----
+  {
+    const float* ap = h0 + (wr0 + i) * TS + k;
+    const float* bp = w1l + (jt0 + i) * W1S + k;
+    const f32x4 acc = shaped_chain1<H1 / 4>(ap, 4, bp, 4);
+    #pragma unroll
+    for (int r = 0; r < 4; ++r)
+      h1[(wr0 + k * 4 + r) * TS + jt0 + i] = act_apply(act1, acc[r] + b1v);
+  }
+  __syncthreads();
+  // ---- forward layer 2 (head, out <= 16: one column tile, waves 0-1) ----
+  if (jt0 == 0) {
+    const float* ap = h1 + (wr0 + i) * TS + k;
+    const float* bp = w2l + i * W2S + k;
+    const f32x4 acc = shaped_chain1<H2 / 4>(ap, 4, bp, 4);
+    if (i < D) {
+      #pragma unroll
+      for (int r = 0; r < 4; ++r)
+        h2[(wr0 + k * 4 + r) * OS + i] = act_apply(act2, acc[r] + b2v);
+    }
+  }
+  __syncthreads();
+
+  // ---- seed the head dZ tile [ROWS][16] (columns >= D are zero) ----
+  if constexpr (GAUSS) {
+    // Gaussian-PPO seed: loss + pending-KL + dlog_std partials and dmean
+    const float inv_b = 1.f / (float)batch;
+    if (tid < ROWS) {
+      const int row = row0 + tid;
+      float lossr = 0.f, klr = 0.f, c = 0.f;
+      if (row < batch) {
+        float base = 0.5f * (float)D * LOG_2PI;
+        float q = 0.f;
+        for (int d = 0; d < D; ++d) {
+          const float ls = lsl[d];
+          base += ls;
+          const float sg = __expf(ls);
+          const float diff = actl[tid * AS + d] - h2[tid * OS + d];
+          const float z = diff / sg;
+          q += z * z;
+        }
+        const float logp = -0.5f * q - base;
+        klr = olp - logp;
+        float lr_;
+        c = dlogp_coeff(1, logp, olp, advv, gargs.clip, &lr_) * inv_b;
+        lossr = lr_ * inv_b;
+      }
+      cbuf[tid] = c;
+      lbuf[tid] = lossr;
+      kbuf[tid] = klr;
+    }
+    __syncthreads();
+    #pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int r = ar + 16 * h;
+      float v = 0.f;
+      if (ad < D && row0 + r < batch) {
+        const float inv_s2 = __expf(-2.f * lsl[ad]);
+        const float diff = actl[r * AS + ad] - h2[r * OS + ad];
+        v = cbuf[r] * diff * inv_s2;
+      }
+      dza[r * TS + ad] = v;
+    }
+    // the two serial sums sit on waves that hold no head wgrad tile:
+    // dlog_std partials -> ws pseudo-layer (fixed row order), wave 2
+    if (tid >= 128 && tid - 128 < D) {
+      const int d = tid - 128;
+      const float inv_s2 = __expf(-2.f * lsl[d]);
+      float acc = 0.f;
+      for (int r = 0; r < ROWS; ++r) {
+        if (row0 + r < batch) {
+          const float diff = actl[r * AS + d] - h2[r * OS + d];
+          acc += cbuf[r] * (diff * diff * inv_s2 - 1.f);
+        }
+      }
+      wsp[(long)(gargs.dls_off + d) * WSN] = acc;
+    }
+    if (tid == 192) {  // wave 3
+      float sl = 0.f, sk = 0.f;
+      for (int r = 0; r < ROWS; ++r) {
+        sl += lbuf[r];
+        sk += kbuf[r];
+      }
+      loss_partials[bx] = sl;
+      gargs.kl_partials[bx] = sk;
+    }
+  } else {
+    // value-MSE seed (out == 1): dZ = 2 (v - ret) / B, block loss partial
+    const float inv_b = 2.f / (float)batch;
+    float loss_acc = 0.f;
+    if (ad >= 1) {
+      dza[ar * TS + ad] = 0.f;
+      dza[(ar + 16) * TS + ad] = 0.f;
+    }
+    if (tid < ROWS) {
+      float v = 0.f;
+      if (row0 + tid < batch) {
+        const float diff = h2[tid * OS] - retv;
+        v = diff * inv_b;
+        loss_acc += diff * diff;
+      }
+      dza[tid * TS] = v;
+    }
+    // deterministic block loss partial (fixed wave order)
+    loss_acc = wave_reduce_sum(loss_acc);
+    if (lane == 0) lred[wave] = loss_acc;
+  }
+  __syncthreads();
+  if (!GAUSS && tid == 0) {
+    loss_partials[bx] =
+        ((lred[0] + lred[1]) + (lred[2] + lred[3])) / (float)batch;
+  }
+
+  // ---- layer 2 backward: wgrad (out x H2: tiles on waves 0-1), bias
+  // partial, dgrad into dzb with tanh'/relu' of h1 fused ----
+  {
+    float* lw = wsp + (long)args.layer_off[2] * WSN;
+    if (wave < 2) {
+      const int jt = wave * 16;
+      const f32x4 acc = shaped_chain1<ROWS / 4>(dza + k * TS + i, 4 * TS,
+                                                h1 + k * TS + jt + i, 4 * TS);
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int orow = k * 4 + r;
+        if (orow < D) lw[((long)orow * H2 + jt + i) * WSN] = acc[r];
+      }
+    }
+    shaped_bias_partial<ROWS>(dza, D, tid, lw + (long)D * H2 * WSN, WSN);
+
+    const int nk = (D + 3) >> 2;  // <= 4
+    const int j = jt0 + i;
+    const float* ap = dza + (wr0 + i) * TS + k;
+    const float* bp = w2l + k * W2S + j;
+    f32x4 acc;
+    switch (nk) {
+      case 1: acc = shaped_chain1<1>(ap, 4, bp, 4 * W2S); break;
+      case 2: acc = shaped_chain1<2>(ap, 4, bp, 4 * W2S); break;
+      case 3: acc = shaped_chain1<3>(ap, 4, bp, 4 * W2S); break;
+      default: acc = shaped_chain1<4>(ap, 4, bp, 4 * W2S); break;
+    }
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = wr0 + k * 4 + r;
+      dzb[rr * TS + j] = acc[r] * act_grad_from_y(act1, h1[rr * TS + j]);
+    }
+  }
+  __syncthreads();
+
+  // ---- layer 1 backward: wgrad (H2 x H1: two tiles per wave sharing the
+  // X operand), bias partial, dgrad (two column tiles) into dza ----
+  {
+    float* lw = wsp + (long)args.layer_off[1] * WSN;
+    {
+      const int jt = wave * 16;
+      const float* bp = h0 + k * TS + jt + i;
+      f32x4 acc0, acc1;
+      shaped_chain2<ROWS / 4>(dzb + k * TS + i, dzb + k * TS + 16 + i, 4 * TS,
+                              bp, bp, 4 * TS, acc0, acc1);
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int orow = k * 4 + r;
+        lw[((long)orow * H1 + jt + i) * WSN] = acc0[r];
+        lw[((long)(orow + 16) * H1 + jt + i) * WSN] = acc1[r];
+      }
+    }
+    shaped_bias_partial<ROWS>(dzb, H2, tid, lw + (long)H2 * H1 * WSN, WSN);
+
+    const int j = jt0 + i;
+    const float* ap = dzb + (wr0 + i) * TS + k;
+    const float* bp = w1l + k * W1S + j;
+    f32x4 acc0, acc1;
+    shaped_chain2<H2 / 4>(ap, ap, 4, bp, bp + 32, 4 * W1S, acc0, acc1);
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rr = wr0 + k * 4 + r;
+      dza[rr * TS + j] = acc0[r] * act_grad_from_y(act0, h0[rr * TS + j]);
+      dza[rr * TS + j + 32] =
+          acc1[r] * act_grad_from_y(act0, h0[rr * TS + j + 32]);
+    }
+  }
+  __syncthreads();
+
+  // ---- layer 0 backward: wgrad only (H1 x in_d; nobody reads dX).  The
+  // 4 * n_jt tiles are dealt over the waves as in the generic body, t =
+  // wave + 4 m ----
+  {
+    float* lw = wsp + (long)args.layer_off[0] * WSN;
+    const int n_jt = in16 >> 4;  // 1..4
+    auto tile_it = [n_jt](int t) {
+      return n_jt == 1 ? t : n_jt == 2 ? t >> 1 : n_jt == 3 ? t / 3 : t >> 2;
+    };
+    auto store = [&](const f32x4& acc, int it, int jt) {
+      const int col = jt + i;
+      if (col < in_d) {
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int orow = it * 16 + k * 4 + r;
+          lw[((long)orow * in_d + col) * WSN] = acc[r];
+        }
+      }
+    };
+    for (int m = 0; m < n_jt; m += 2) {
+      const int t0 = wave + 4 * m;
+      const int it0 = tile_it(t0), jtA = (t0 - it0 * n_jt) * 16;
+      if (m + 1 < n_jt) {
+        const int t1 = t0 + 4;
+        const int it1 = tile_it(t1), jtB = (t1 - it1 * n_jt) * 16;
+        f32x4 acc0, acc1;
+        shaped_chain2<ROWS / 4>(dza + k * TS + it0 * 16 + i,
+                                dza + k * TS + it1 * 16 + i, 4 * TS,
+                                xt + k * TS + jtA + i, xt + k * TS + jtB + i,
+                                4 * TS, acc0, acc1);
+        store(acc0, it0, jtA);
+        store(acc1, it1, jtB);
+      } else {
+        const f32x4 acc =
+            shaped_chain1<ROWS / 4>(dza + k * TS + it0 * 16 + i, 4 * TS,
+                                    xt + k * TS + jtA + i, 4 * TS);
+        store(acc, it0, jtA);
+      }
+    }
+    shaped_bias_partial<ROWS>(dza, H1, tid, lw + (long)H1 * in_d * WSN, WSN);
+  }
+}
+
+// The twin launch on the shaped body: grid (fb, 2), blockIdx.y 0 the
+// Gaussian-PPO half, 1 the value-MSE half, same argument block, workspace
+// layout and partials as mlp_bwd_fused_twin_f32<32>.
+__global__ __launch_bounds__(256) void mlp_bwd_fused_twin_shaped_f32(
+    MLPBwdTwinArgs a) {
+  extern __shared__ float smem[];
+  if (blockIdx.y == 0) {
+    mlp_bwd_fused_shaped_body<32, 64, 32, true>(
+        a.pol, a.x, a.pol_ws, nullptr, a.pol_loss_partials, a.gauss, smem,
+        blockIdx.x, gridDim.x);
+  } else {
+    mlp_bwd_fused_shaped_body<32, 64, 32, false>(
+        a.val, a.x, a.val_ws, a.returns, a.val_loss_partials, GaussSeedArgs{},
+        smem, blockIdx.x, gridDim.x);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // wide-net single-layer kernels: 2D grids (row blocks x 64-col groups).
 // The fused multi-layer kernel keeps every output column of a row tile
 // in one block, which leaves most of the chip idle for [*,256,256,*]
@@ -964,6 +1464,15 @@ void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
   else
     hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32>), dim3(n_blocks, 2),
                        dim3(256), lds_bytes, stream, a);
+}
+
+// Both nets must be [in <= 64, 64, 32, out <= 16] fp32 on 32-row blocks
+// (the caller checks); LDS is mlp_bwd_fused_shaped_lds(in).
+void launch_mlp_bwd_fused_twin_shaped(const MLPBwdTwinArgs& a, int n_blocks,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(mlp_bwd_fused_twin_shaped_f32, dim3(n_blocks, 2),
+                     dim3(256), mlp_bwd_fused_shaped_lds(a.pol.dims[0]), stream,
+                     a);
 }
 
 void launch_mlp_layer_fwd_wide(const float* x, const float* W, const float* B,
