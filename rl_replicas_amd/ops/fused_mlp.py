@@ -41,7 +41,12 @@ _ACT_CODE = {
     nn.ReLU: ACT_RELU,
 }
 
-MAX_WIDTH = 256  # widest layer the LDS-staged kernels support
+# MLP_MAX_WIDTH / MLP_MAX_LAYERS of ops/hip/common.h: the widest and the
+# deepest net the kernels take.  Kept here so that hosts without the
+# extension classify nets the same way; a GPU test holds them equal to the
+# extension's fused_mlp_limits().
+MAX_WIDTH = 256
+MAX_LAYERS = 5
 
 
 def _extract_layers(mlp) -> Optional[tuple]:
@@ -71,7 +76,7 @@ def _extract_layers(mlp) -> Optional[tuple]:
         biases.append(lin.bias)
         acts.append(code)
         i += 2
-    if not ok or not weights:
+    if not ok or not 1 <= len(weights) <= MAX_LAYERS:
         mlp._fused_layout = ()
         return None
     if max(w.shape[0] for w in weights) > MAX_WIDTH or weights[0].shape[1] > MAX_WIDTH:

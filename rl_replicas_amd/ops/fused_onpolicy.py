@@ -1,18 +1,31 @@
 """Fully-fused on-policy update loops (GPU hot path).
 
-On the GPU the PPO/VPG policy-update loop and the value-function loop
-bypass torch autograd entirely: per iteration
-    fused MLP forward (1 kernel, saves activations)
-    fused loss fwd+bwd (1 kernel -> dmean/dlogits [+dlog_std] + loss)
-    fused MLP backward (L merged dgrad/wgrad kernels + 1 reduction)
-    fused multi-tensor Adam (1 kernel)
-    [PPO] fused forward + approx-KL kernel for the early-stop test
-~9 kernels per policy iteration instead of the ~40 torch-eager ones,
-with identical semantics to the eager path (same update order, same
-KL early stop, torch-exact min/clamp tie gradients — see
-loss_kernels.hip).  The DP gradient all-reduce hook runs between
-backward and step exactly as in the eager path, and the hipGraph
-variants keep it eager between captured pre/post graphs.
+On the GPU the PPO/VPG policy update and the value-function loop bypass
+torch autograd entirely.  From fastest to most general, one PPO epoch's
+update runs as:
+
+  twin graph (_GraphedPPOTwin): policy iteration i and value iteration i
+      share two launches — a twin kernel that runs forward, loss seed and
+      whole-net backward of both nets with LDS-resident activations, and a
+      twin reduce+Adam with the KL early-stop gate folded in.  Narrow fp32
+      identity-head Gaussian policy, narrow value net, both on FusedAdam,
+      P <= V, no per-iteration collectives.
+  separate graphs (_GraphedPPO, _GraphedValueLoop): the same two-kernel
+      iterations per net where each is eligible (chunked capture for the
+      policy's early stop); otherwise a captured per-iteration pipeline of
+      fused forward, fused loss fwd+bwd, fused MLP backward and fused
+      multi-tensor Adam, with a fused approximate-KL kernel for the early
+      stop.  Under data parallelism each iteration splits into pre/post
+      graphs around the eager gradient all-reduce.
+  eager loops (ppo_update, vpg_update, value_update): that pipeline
+      launched from the host, when graphs are disabled or the optimizer is
+      not FusedAdam.
+
+All of them have the semantics of the eager torch path (same update order,
+same KL early stop, torch-exact min/clamp tie gradients — see
+loss_kernels.hip).  Which nets the whole-net kernels take is the
+extension's answer (fused_bwd_fits, fused_mlp_limits), never re-derived
+here.
 
 Falls back silently (returns False from `supported`) for policies that
 are not MLP-backed Gaussian/Categorical or are not on GPU.
@@ -20,6 +33,8 @@ are not MLP-backed Gaussian/Categorical or are not on GPU.
 from __future__ import annotations
 
 import logging
+import math
+import os
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -59,12 +74,51 @@ def supported(policy, obs: Tensor) -> bool:
     mlp = _mlp_of(policy)
     if mlp is None or _extract_layers(mlp) is None:
         return False
-    if kind == "gaussian" and policy.log_std.numel() > 512:
-        # loss kernel bound (GAUSS_MAX_D, loss_kernels.hip); the MLP
-        # kernels cap widths at 256 anyway so this is never the binding
-        # constraint in practice
+    if kind == "gaussian" and policy.log_std.numel() > _limits()[3]:
+        # loss kernel bound (GAUSS_MAX_D); the MLP kernels cap widths at
+        # 256 anyway so this is never the binding constraint in practice
         return False
     return True
+
+
+def _limits():
+    """(max layers, max width, narrow-kernel width = fused-iteration action
+    dim cap, Gaussian loss action-dim cap) of the extension."""
+    return ops._load_extension().fused_mlp_limits()
+
+
+def _fused_bwd_fits(in_dim: int, weights, reserve: int = 0):
+    """Whether the whole-net fused backward takes the net, (with a separate
+    forward, with the forward in the kernel) — the extension's own gate.
+    `reserve` keeps argument-block slots free (the log_std pseudo-layer)."""
+    dims = [int(in_dim)] + [int(w.shape[0]) for w in weights]
+    return ops._load_extension().fused_bwd_fits(dims, reserve)
+
+
+def _assign_grads(weights, biases, grads) -> None:
+    """.grad of the net's parameters from a backward binding's result
+    [dx, dW..., db..., (loss)]."""
+    n = len(weights)
+    for w, dw in zip(weights, grads[1 : 1 + n]):
+        w.grad = dw
+    for b, db in zip(biases, grads[1 + n : 1 + 2 * n]):
+        b.grad = db
+
+
+def _policy_loss(policy, kind: str, mode: int, out: Tensor, actions: Tensor,
+                 old_logp: Tensor, advantages: Tensor, clip: float):
+    """Fused loss fwd+bwd on the net output `out`: (grad_out, extra_grads,
+    scalars), extra_grads the (param, grad) pairs outside the MLP."""
+    ext = ops._load_extension()
+    if kind == "gaussian":
+        dmean, dlog_std, scalars = ext.gaussian_policy_loss(
+            out, actions, old_logp, advantages, policy.log_std.data, clip, mode
+        )
+        return dmean, [(policy.log_std, dlog_std)], scalars
+    dlogits, scalars = ext.categorical_policy_loss(
+        out, actions, old_logp, advantages, clip, mode
+    )
+    return dlogits, [], scalars
 
 
 def _forward_saved(mlp, obs: Tensor):
@@ -88,11 +142,7 @@ def _backward_and_step(policy, mlp, obs, grad_out, hidden, final_out, weights,
     ext = ops._load_extension()
     grads = ext.mlp_backward(grad_out, obs, list(weights), list(biases),
                              list(hidden), final_out, acts, ops.compute_bf16())
-    n = len(weights)
-    for w, dw in zip(weights, grads[1 : 1 + n]):
-        w.grad = dw
-    for b, db in zip(biases, grads[1 + n :]):
-        b.grad = db
+    _assign_grads(weights, biases, grads)
     for param, grad in extra_grads:
         param.grad = grad
     all_reduce_hook(policy)
@@ -105,9 +155,6 @@ def _fast_diagnostics(policy, kind: str, obs: Tensor, actions: Tensor):
     ppo.py:163-170).  For the state-independent-sigma Gaussian the mean
     entropy is CLOSED FORM (sum(log_std) + D/2*(1+log 2pi)); logp comes
     from the fused logp kernel."""
-    import math
-
-    ext = ops._load_extension()
     logp = _old_logp(policy, kind, obs, actions)
     if kind == "gaussian":
         d = policy.log_std.numel()
@@ -149,8 +196,6 @@ def _old_logp(policy, kind: str, obs: Tensor, actions: Tensor) -> Tensor:
 
 
 def _graphs_common(algo) -> bool:
-    import os
-
     return os.environ.get("RL_REPLICAS_AMD_DISABLE_GRAPHS", "0") != "1"
 
 
@@ -171,8 +216,6 @@ def _dp_active(algo) -> bool:
     Replicate-mode DP runs the whole global batch locally (zero
     per-iteration collectives), so its loops capture whole like
     single-process."""
-    import os
-
     from rl_replicas_amd.parallel.ddp import distributed_is_active
 
     if getattr(algo, "_dp_replicate", False):
@@ -200,12 +243,9 @@ def _ensure_adam_state(optimizer) -> List[Tensor]:
 
 
 def _fwd_in_kernel_fits(weights) -> bool:
-    """LDS budget of the fused kernels that run the forward themselves
-    (3 + L activation tiles of 32 rows + the padded weight image) —
-    mirrors the C++ gate (backward tiles are 32 rows at every batch:
-    bwd_fused_rows)."""
-    whole_w = sum(w.shape[0] * (w.shape[1] + 1) for w in weights)
-    return ((3 + len(weights)) * 32 * 68 + whole_w) * 4 <= 100 * 1024
+    """Whether the fused kernels that run the forward themselves take the
+    net (its weight image and their activation tiles fit the LDS budget)."""
+    return _fused_bwd_fits(weights[0].shape[1], weights)[1]
 
 
 def _mega_eligible(policy, kind: str, obs: Tensor) -> bool:
@@ -216,10 +256,8 @@ def _mega_eligible(policy, kind: str, obs: Tensor) -> bool:
     weights, _, acts = _extract_layers(_mlp_of(policy))
     return (
         acts[-1] == 0  # identity head
-        and len(weights) + 1 <= 5
-        and policy.log_std.numel() <= 64
-        and max([obs.shape[1]] + [w.shape[0] for w in weights]) <= 64
-        and _fwd_in_kernel_fits(weights)
+        and policy.log_std.numel() <= _limits()[2]
+        and _fused_bwd_fits(obs.shape[1], weights, reserve=1)[1]
     )
 
 
@@ -283,27 +321,14 @@ class _GraphedPPO:
 
         def loss_bwd_from(out, hidden, weights, biases, acts):
             """loss + gradients from an already-computed saved forward."""
-            if kind == "gaussian":
-                dmean, dlog_std, scalars = ext.gaussian_policy_loss(
-                    out, self.actions, self.old_logp, self.adv,
-                    policy.log_std.data, clip, MODE_PPO,
-                )
-                extra = [(policy.log_std, dlog_std)]
-                grad_out = dmean
-            else:
-                dlogits, scalars = ext.categorical_policy_loss(
-                    out, self.actions, self.old_logp, self.adv, clip, MODE_PPO
-                )
-                extra = []
-                grad_out = dlogits
+            grad_out, extra, scalars = _policy_loss(
+                policy, kind, MODE_PPO, out, self.actions, self.old_logp,
+                self.adv, clip,
+            )
             grads = ext.mlp_backward(grad_out, self.obs, list(weights),
                                      list(biases), list(hidden), out, acts,
                                      ops.compute_bf16())
-            n = len(weights)
-            for w, dw in zip(weights, grads[1 : 1 + n]):
-                w.grad = dw
-            for b, db in zip(biases, grads[1 + n :]):
-                b.grad = db
+            _assign_grads(weights, biases, grads)
             for param, grad in extra:
                 param.grad = grad
             return scalars
@@ -354,11 +379,8 @@ class _GraphedPPO:
                 m2l, v2l, step0, hp = adam_arg_lists(
                     policy.optimizer, weights0, biases0
                 )
+                # created by _ensure_adam_state above
                 ls_state = policy.optimizer.state[policy.log_std]
-                if len(ls_state) == 0:
-                    ls_state["step"] = torch.zeros((), dtype=torch.float32, device=dev)
-                    ls_state["exp_avg"] = torch.zeros_like(policy.log_std)
-                    ls_state["exp_avg_sq"] = torch.zeros_like(policy.log_std)
                 ls_m, ls_v = ls_state["exp_avg"], ls_state["exp_avg_sq"]
                 scratch_loss = torch.zeros(1, device=dev)
 
@@ -424,12 +446,10 @@ class _GraphedPPO:
             # while keeping host syncs at one gate readback per chunk
             # (vs per-iteration replay+sync, or one full-loop graph
             # that always runs all 80)
-            import os as _os
-
             # ladder on the bench: 5 -> 898K, 10 -> 880K, 20 -> 834K
             # env-steps/s (steady state stops early, so smaller chunks
             # waste fewer masked iterations)
-            CHUNK = int(_os.environ.get("RL_REPLICAS_AMD_PPO_CHUNK", "5"))
+            CHUNK = int(os.environ.get("RL_REPLICAS_AMD_PPO_CHUNK", "5"))
             self.chunks = []
             for start in range(0, num_iters, CHUNK):
                 count = min(CHUNK, num_iters - start)
@@ -503,11 +523,7 @@ def _value_iter_wide(algo, obs: Tensor, returns: Tensor, adam=None) -> Tensor:
     grads = ext.mlp_backward(dv.view(out.shape), obs, list(weights),
                              list(biases), list(hidden), out, acts,
                              ops.compute_bf16())
-    n = len(weights)
-    for w, dw in zip(weights, grads[1 : 1 + n]):
-        w.grad = dw
-    for b, db in zip(biases, grads[1 + n :]):
-        b.grad = db
+    _assign_grads(weights, biases, grads)
     return scalars  # [1], same shape contract as value_mlp_backward's loss
 
 
@@ -535,11 +551,7 @@ class _GraphedValueLoop:
             grads = ext.value_mlp_backward(self.obs, list(weights), list(biases),
                                            list(hidden), out, acts, self.returns,
                                            ops.compute_bf16())
-            n = len(weights)
-            for w, dw in zip(weights, grads[1 : 1 + n]):
-                w.grad = dw
-            for b, db in zip(biases, grads[1 + n : 1 + 2 * n]):
-                b.grad = db
+            _assign_grads(weights, biases, grads)
             return grads[-1]
 
         state = [p.data for p in vf.parameters()]
@@ -563,9 +575,8 @@ class _GraphedValueLoop:
                 vf.optimizer, weights0, biases0
             )
 
-            # DO_FWD stages L extra activation tiles in LDS — mirror
-            # the C++ budget gate so deep narrow nets fall back to the
-            # separate-forward form instead of tripping the TORCH_CHECK
+            # DO_FWD stages L extra activation tiles in LDS: deep narrow
+            # nets it cannot hold take the separate-forward form
             fp32 = ops.compute_bf16() == 0 and _fwd_in_kernel_fits(weights0)
             dummy = torch.empty(0, device=obs0.device)
 
@@ -758,9 +769,8 @@ def _get_cached_graph(algo, attr: str, key, builder):
     return graph
 
 
-def _ppo_prelude(algo, obs: Tensor, actions: Tensor, advantages: Tensor):
-    """Kernel-layout inputs, the pre-update diagnostics and old_logp."""
-    policy = algo.policy
+def _kernel_inputs(policy, obs: Tensor, actions: Tensor, advantages: Tensor):
+    """Kernel-layout inputs and the pre-update diagnostics."""
     kind = _policy_kind(policy)
     obs = obs.contiguous()
     if kind == "gaussian":
@@ -768,9 +778,15 @@ def _ppo_prelude(algo, obs: Tensor, actions: Tensor, advantages: Tensor):
     else:
         actions_k = actions.contiguous().view(-1)
     advantages = advantages.contiguous()
-
     diagnostics = _fast_diagnostics(policy, kind, obs, actions_k)
+    return kind, obs, actions_k, advantages, diagnostics
 
+
+def _ppo_prelude(algo, obs: Tensor, actions: Tensor, advantages: Tensor):
+    """_kernel_inputs plus old_logp."""
+    kind, obs, actions_k, advantages, diagnostics = _kernel_inputs(
+        algo.policy, obs, actions, advantages
+    )
     with torch.no_grad():
         old_logp = _old_logp(algo.old_policy, kind, obs, actions_k)
     return kind, obs, actions_k, advantages, diagnostics, old_logp
@@ -785,8 +801,6 @@ def ppo_twin_eligible(algo, obs: Tensor) -> bool:
     RL_REPLICAS_AMD_TWIN_SHAPED=0 keeps the twin launch on the generic
     kernel where the [in, 64, 32, out] shaped one would run (the
     extension reads it per call; a captured graph keeps its kernel)."""
-    import os
-
     if os.environ.get("RL_REPLICAS_AMD_PPO_TWIN", "1") == "0":
         return False
     policy = algo.policy
@@ -870,18 +884,9 @@ def ppo_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[s
     approximate_kl = torch.zeros((), device=obs.device)
     for i in range(algo.num_policy_gradients):
         out, hidden, weights, biases, acts = _forward_saved(mlp, obs)
-        if kind == "gaussian":
-            dmean, dlog_std, scalars = ext.gaussian_policy_loss(
-                out, actions_k, old_logp, advantages, policy.log_std.data, clip, MODE_PPO
-            )
-            extra = [(policy.log_std, dlog_std)]
-            grad_out = dmean
-        else:
-            dlogits, scalars = ext.categorical_policy_loss(
-                out, actions_k, old_logp, advantages, clip, MODE_PPO
-            )
-            extra = []
-            grad_out = dlogits
+        grad_out, extra, scalars = _policy_loss(
+            policy, kind, MODE_PPO, out, actions_k, old_logp, advantages, clip
+        )
         if loss_before is None:
             loss_before = scalars[0]
         _backward_and_step(
@@ -909,33 +914,17 @@ def ppo_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[s
 
 def vpg_update(algo, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[str, float]:
     """Single VPG policy step (vpg.py:194-207) on the fused path."""
-    ext = ops._load_extension()
     policy = algo.policy
-    kind = _policy_kind(policy)
     mlp = _mlp_of(policy)
-    obs = obs.contiguous()
-    if kind == "gaussian":
-        actions_k = actions.contiguous().view(obs.shape[0], -1)
-    else:
-        actions_k = actions.contiguous().view(-1)
-    advantages = advantages.contiguous()
-
-    diagnostics = _fast_diagnostics(policy, kind, obs, actions_k)
+    kind, obs, actions_k, advantages, diagnostics = _kernel_inputs(
+        policy, obs, actions, advantages
+    )
 
     out, hidden, weights, biases, acts = _forward_saved(mlp, obs)
-    dummy = torch.empty(0, device=obs.device)
-    if kind == "gaussian":
-        dmean, dlog_std, scalars = ext.gaussian_policy_loss(
-            out, actions_k, dummy, advantages, policy.log_std.data, 0.0, MODE_VPG
-        )
-        extra = [(policy.log_std, dlog_std)]
-        grad_out = dmean
-    else:
-        dlogits, scalars = ext.categorical_policy_loss(
-            out, actions_k, dummy, advantages, 0.0, MODE_VPG
-        )
-        extra = []
-        grad_out = dlogits
+    dummy = torch.empty(0, device=obs.device)  # VPG has no old_logp
+    grad_out, extra, scalars = _policy_loss(
+        policy, kind, MODE_VPG, out, actions_k, dummy, advantages, 0.0
+    )
     _backward_and_step(
         policy, mlp, obs, grad_out, hidden, out, weights, biases, acts, extra,
         algo._all_reduce_gradients,
@@ -972,11 +961,7 @@ def value_update(algo, obs: Tensor, returns: Tensor, num_iters: int) -> float:
                                            list(hidden), out, acts, returns,
                                            ops.compute_bf16())
             losses.append(grads[-1])
-            n = len(weights)
-            for w, dw in zip(weights, grads[1 : 1 + n]):
-                w.grad = dw
-            for b, db in zip(biases, grads[1 + n : 1 + 2 * n]):
-                b.grad = db
+            _assign_grads(weights, biases, grads)
         algo._all_reduce_gradients(vf)
         vf.optimizer.step()
     return float(torch.cat(losses).mean())
@@ -999,13 +984,7 @@ def value_mode(algo, obs: Tensor) -> Optional[str]:
     weights, biases, acts = layout
     if weights[-1].shape[0] != 1:
         return None
-    max_width = max(obs.shape[-1], max(w.shape[0] for w in weights))
-    whole_w = sum(w.shape[0] * (w.shape[1] + 1) for w in weights)
-    if (
-        acts[-1] == ACT_IDENTITY
-        and max_width <= 64
-        and (3 * 32 * 68 + whole_w) * 4 <= 100 * 1024
-    ):
+    if acts[-1] == ACT_IDENTITY and _fused_bwd_fits(obs.shape[-1], weights)[0]:
         return "narrow"
     return "wide"
 

@@ -15,30 +15,24 @@
 
 // kernel declarations (defined in the .hip translation units)
 void launch_mlp_fwd(const MLPArgs& args, const float* x, int save_hidden,
-                    int rows, int maxw, int n_blocks, int wstage_mode,
-                    size_t lds_bytes, int compute_bf16, hipStream_t stream);
+                    int rows, int n_blocks, size_t lds_bytes, int compute_bf16,
+                    hipStream_t stream);
 void launch_mlp_bwd_layer(const float* dy, const float* y, const float* xin,
                           const float* W, float* dx, float* ws, long ws_stride,
                           int batch, int out_d, int in_d, int act, int rows,
-                          int maxw, int n_blocks, int wstage_mode,
-                          size_t lds_bytes, hipStream_t stream);
+                          int n_blocks, size_t lds_bytes, hipStream_t stream);
 void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
                           const float* dy, float* dx, float* ws,
                           const float* mse_returns, float* loss_partials,
                           size_t lds_bytes, int n_blocks, int compute_bf16,
-                          hipStream_t stream, int rows, int do_fwd = 0,
+                          hipStream_t stream, int do_fwd = 0,
                           GaussSeedArgs gargs = GaussSeedArgs{},
                           int need_dx = 1);
-// Backward tiles stay at 32 rows: 16-row tiles made stage-1 faster but
-// DOUBLED the partial-row count, pushing the (latency-bound) reduce
-// from 10.3 to 17.8 us — a measured net loss.  (The FORWARD still uses
-// 16-row tiles below 8K rows; its cost has no reduce to pay.)
-inline int bwd_fused_rows(int batch) { (void)batch; return 32; }
 __global__ void mlp_grad_reduce_onepass_f32(ReduceAllArgs a);
 void launch_mlp_grad_reduce_adam(const ReduceAdamArgs& a, long grand,
                                  hipStream_t stream);
 void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
-                               int n_blocks, int rows, hipStream_t stream);
+                               int n_blocks, hipStream_t stream);
 void launch_mlp_bwd_fused_twin_shaped(const MLPBwdTwinArgs& a, int n_blocks,
                                       hipStream_t stream);
 size_t mlp_bwd_fused_shaped_lds(int in_d);
@@ -158,21 +152,228 @@ void check_f32_gpu(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e));    \
   } while (0)
 
-// argument block of the merged reduce+Adam kernels for one net: m/v are
-// ordered [weights..., biases...]
+// Backward tiles stay at 32 rows: 16-row tiles made stage-1 faster but
+// DOUBLED the partial-row count, pushing the (latency-bound) reduce
+// from 10.3 to 17.8 us — a measured net loss.  (The FORWARD still uses
+// 16-row tiles below 8K rows; its cost has no reduce to pay.)
+constexpr int BWD_FUSED_ROWS = 32;
+
+// The one validated description of a net handed to a binding: layer widths
+// and the flat layout of its gradient partials — the layers' (od*id + od)
+// segments in layer order.  whole_w = floats of the padded whole-net LDS
+// weight image ([out][in + 1] per layer).
+struct NetLayout {
+  int L = 0;
+  int dims[MLP_MAX_LAYERS + 1] = {};
+  int64_t totals[MLP_MAX_LAYERS] = {};
+  int64_t layer_off[MLP_MAX_LAYERS] = {};
+  int64_t grand = 0;
+  size_t whole_w = 0;
+  int max_width = 0;
+};
+
+// dims = [in, hidden..., out]; `reserve` keeps that many of the fixed
+// argument-block slots free (the policy path's log_std pseudo-layer)
+NetLayout net_layout(const std::vector<int64_t>& dims, int width_cap,
+                     int reserve = 0) {
+  NetLayout n;
+  n.L = (int)dims.size() - 1;
+  TORCH_CHECK(n.L >= 1 && n.L + reserve <= MLP_MAX_LAYERS,
+              "unsupported layer count ", n.L, " (at most ",
+              MLP_MAX_LAYERS - reserve, ")");
+  for (int l = 0; l <= n.L; ++l) {
+    TORCH_CHECK(dims[l] >= 1 && dims[l] <= width_cap, "layer width ", dims[l],
+                " outside [1, ", width_cap, "]");
+    n.dims[l] = (int)dims[l];
+    n.max_width = std::max(n.max_width, n.dims[l]);
+  }
+  for (int l = 0; l < n.L; ++l) {
+    n.totals[l] = (int64_t)n.dims[l + 1] * n.dims[l] + n.dims[l + 1];
+    n.layer_off[l] = n.grand;
+    n.grand += n.totals[l];
+    n.whole_w += (size_t)n.dims[l + 1] * (n.dims[l] + 1);
+  }
+  return n;
+}
+
+// every check a binding makes of (input width, weights, biases, acts)
+NetLayout net_layout(int64_t in_dim, const std::vector<torch::Tensor>& weights,
+                     const std::vector<torch::Tensor>& biases,
+                     const std::vector<int64_t>& acts, int width_cap,
+                     int reserve = 0) {
+  TORCH_CHECK(biases.size() == weights.size() && acts.size() == weights.size(),
+              "weights/biases/acts length mismatch");
+  std::vector<int64_t> dims{in_dim};
+  for (size_t l = 0; l < weights.size(); ++l) {
+    check_f32_gpu(weights[l], "weight");
+    check_f32_gpu(biases[l], "bias");
+    TORCH_CHECK(weights[l].dim() == 2 && weights[l].size(1) == dims[l],
+                "weight shape mismatch at layer ", l);
+    TORCH_CHECK(biases[l].numel() == weights[l].size(0),
+                "bias shape mismatch at layer ", l);
+    dims.push_back(weights[l].size(0));
+  }
+  return net_layout(dims, width_cap, reserve);
+}
+
+NetLayout net_layout(const torch::Tensor& x,
+                     const std::vector<torch::Tensor>& weights,
+                     const std::vector<torch::Tensor>& biases,
+                     const std::vector<int64_t>& acts, int width_cap,
+                     int reserve = 0) {
+  check_f32_gpu(x, "x");
+  TORCH_CHECK(x.dim() == 2, "x must be 2-D");
+  return net_layout(x.size(1), weights, biases, acts, width_cap, reserve);
+}
+
+// the w/b/dims/acts/n_layers fields every net-carrying argument block has
+template <class Args>
+void fill_net(Args& a, const NetLayout& n,
+              const std::vector<torch::Tensor>& weights,
+              const std::vector<torch::Tensor>& biases,
+              const std::vector<int64_t>& acts) {
+  a.n_layers = n.L;
+  a.dims[0] = n.dims[0];
+  for (int l = 0; l < n.L; ++l) {
+    a.w[l] = weights[l].data_ptr<float>();
+    a.b[l] = biases[l].data_ptr<float>();
+    a.dims[l + 1] = n.dims[l + 1];
+    a.acts[l] = (int)acts[l];
+  }
+}
+
+// saved activations of a backward: hidden[l] is layer l's output
+// [batch, dims[l + 1]] for l < L - 1, final_out the last layer's
+void check_saved(const NetLayout& n, int64_t batch,
+                 const std::vector<torch::Tensor>& hidden,
+                 const torch::Tensor& final_out) {
+  TORCH_CHECK((int)hidden.size() == n.L - 1, "hidden must hold ", n.L - 1,
+              " activations, got ", hidden.size());
+  for (int l = 0; l < n.L; ++l) {
+    const torch::Tensor& h = l == n.L - 1 ? final_out : hidden[l];
+    check_f32_gpu(h, "saved activation");
+    TORCH_CHECK(h.numel() == batch * n.dims[l + 1],
+                "saved activation shape mismatch at layer ", l);
+  }
+}
+
+// Adam state of one net for the merged reduce+Adam kernels: m/v ordered
+// [weights..., biases...], shaped like the parameters
+void check_adam_state(const std::vector<torch::Tensor>& weights,
+                      const std::vector<torch::Tensor>& biases,
+                      const std::vector<torch::Tensor>& m,
+                      const std::vector<torch::Tensor>& v,
+                      const torch::Tensor& step) {
+  const size_t L = weights.size();
+  TORCH_CHECK(m.size() == 2 * L && v.size() == 2 * L,
+              "adam m/v must be [weights..., biases...] (2L tensors)");
+  for (size_t i = 0; i < 2 * L; ++i) {
+    const torch::Tensor& p = i < L ? weights[i] : biases[i - L];
+    check_f32_gpu(m[i], "adam m");
+    check_f32_gpu(v[i], "adam v");
+    TORCH_CHECK(m[i].numel() == p.numel() && v[i].numel() == p.numel(),
+                "adam state shape mismatch");
+  }
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == torch::kFloat32 &&
+                  step.numel() == 1,
+              "adam step must be a 1-element fp32 GPU tensor");
+}
+
+// dynamic LDS of the narrow forward (activation ping-pong) and per-layer
+// backward (dZ + x) kernels: two row tiles + a padded weight image
+size_t two_tile_lds(int rows, size_t image_floats) {
+  return ((size_t)2 * rows * (MLP_NARROW_WIDTH + 4) + image_floats) * 4;
+}
+
+// dynamic LDS of the whole-net fused backward: 3 tiles (dZ ping-pong + x),
+// plus one activation tile per layer when the forward runs in the kernel
+size_t fused_bwd_lds(const NetLayout& n, bool fwd_in_kernel) {
+  const size_t act_tiles = (size_t)(fwd_in_kernel ? 3 + n.L : 3);
+  return (act_tiles * BWD_FUSED_ROWS * (MLP_NARROW_WIDTH + 4) + n.whole_w) * 4;
+}
+
+// whether the whole-net fused backward takes this net — the gate of
+// mlp_backward, the check of the bindings that have no other kernel, and
+// what fused_bwd_fits tells Python
+bool fused_bwd_fits(const NetLayout& n, bool fwd_in_kernel) {
+  return n.max_width <= MLP_NARROW_WIDTH &&
+         fused_bwd_lds(n, fwd_in_kernel) <= MLP_LDS_BUDGET;
+}
+
+// whole-net fused-backward argument block with h[] unset (the in-kernel
+// forward keeps activations in LDS); ws_stride = flat elems per partial row
+MLPBwdArgs fill_bwd_args(const torch::Tensor& x,
+                         const std::vector<torch::Tensor>& weights,
+                         const std::vector<torch::Tensor>& biases,
+                         const std::vector<int64_t>& acts,
+                         const NetLayout& n, int64_t ws_stride) {
+  MLPBwdArgs ba{};
+  fill_net(ba, n, weights, biases, acts);
+  ba.batch = (int)x.size(0);
+  ba.ws_stride = ws_stride;
+  for (int l = 0; l < n.L; ++l) ba.layer_off[l] = (int)n.layer_off[l];
+  return ba;
+}
+
+// ... and with the saved activations of a separate forward
+void set_saved(MLPBwdArgs& ba, const NetLayout& n,
+               const std::vector<torch::Tensor>& hidden,
+               const torch::Tensor& final_out) {
+  for (int l = 0; l < n.L; ++l)
+    ba.h[l] = (l == n.L - 1 ? final_out : hidden[l]).data_ptr<float>();
+}
+
+// gradient tensors of a backward and its [dx, dW..., db...] result
+struct GradOut {
+  std::vector<torch::Tensor> dws, dbs;
+  GradOut(const NetLayout& n, const torch::TensorOptions& opts) {
+    for (int l = 0; l < n.L; ++l) {
+      dws.push_back(torch::empty({n.dims[l + 1], n.dims[l]}, opts));
+      dbs.push_back(torch::empty({n.dims[l + 1]}, opts));
+    }
+  }
+  std::vector<torch::Tensor> pack(const torch::Tensor& dx) const {
+    std::vector<torch::Tensor> out{dx};
+    out.insert(out.end(), dws.begin(), dws.end());
+    out.insert(out.end(), dbs.begin(), dbs.end());
+    return out;
+  }
+};
+
+// one-pass deterministic reduction of the partial rows ws[n_blocks][grand]
+// into the gradient tensors
+void launch_reduce_all(const NetLayout& n, const float* ws, int n_blocks,
+                       const GradOut& g, hipStream_t stream) {
+  ReduceAllArgs ra{};
+  ra.ws = ws;
+  ra.stride = n.grand;
+  ra.n_layers = n.L;
+  ra.n_blocks = n_blocks;
+  for (int l = 0; l < n.L; ++l) {
+    ra.dw[l] = g.dws[l].data_ptr<float>();
+    ra.db[l] = g.dbs[l].data_ptr<float>();
+    ra.total[l] = (int)n.totals[l];
+    ra.wsize[l] = n.dims[l + 1] * n.dims[l];
+  }
+  const int rb = (int)std::min<int64_t>(256, (n.grand + 63) / 64);
+  hipLaunchKernelGGL(mlp_grad_reduce_onepass_f32, dim3(rb), dim3(256), 0,
+                     stream, ra);
+  HIP_OK(hipGetLastError());
+}
+
+// argument block of the merged reduce+Adam kernels for one net (m/v as
+// check_adam_state admits them)
 ReduceAdamArgs fill_reduce_adam(const std::vector<torch::Tensor>& weights,
                                 const std::vector<torch::Tensor>& biases,
-                                const std::vector<int64_t>& totals,
-                                const float* ws, long stride, int n_blocks,
+                                const NetLayout& n, const float* ws,
+                                long stride, int n_blocks,
                                 const std::vector<torch::Tensor>& m,
                                 const std::vector<torch::Tensor>& v,
                                 const torch::Tensor& step, double lr,
                                 double beta1, double beta2, double eps,
                                 double weight_decay, double step_delta,
                                 const c10::optional<torch::Tensor>& gate) {
-  const int L = (int)weights.size();
-  TORCH_CHECK((int)m.size() == 2 * L && (int)v.size() == 2 * L,
-              "adam m/v must be [weights..., biases...] (2L tensors)");
+  const int L = n.L;
   ReduceAdamArgs ra{};
   ra.ws = ws;
   ra.stride = stride;
@@ -185,8 +386,8 @@ ReduceAdamArgs fill_reduce_adam(const std::vector<torch::Tensor>& weights,
     ra.mb[l] = m[L + l].data_ptr<float>();
     ra.vw[l] = v[l].data_ptr<float>();
     ra.vb[l] = v[L + l].data_ptr<float>();
-    ra.total[l] = (int)totals[l];
-    ra.wsize[l] = (int)(weights[l].size(0) * weights[l].size(1));
+    ra.total[l] = (int)n.totals[l];
+    ra.wsize[l] = n.dims[l + 1] * n.dims[l];
   }
   ra.step = step.data_ptr<float>();
   ra.lr = (float)lr;
@@ -203,8 +404,7 @@ ReduceAdamArgs fill_reduce_adam(const std::vector<torch::Tensor>& weights,
 // value_mlp_backward)
 void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
                         const std::vector<torch::Tensor>& biases,
-                        const std::vector<int64_t>& totals, const float* ws,
-                        long stride, int n_blocks, int64_t grand,
+                        const NetLayout& n, const float* ws, int n_blocks,
                         const std::vector<torch::Tensor>& m,
                         const std::vector<torch::Tensor>& v,
                         const torch::Tensor& step, double lr, double beta1,
@@ -213,128 +413,39 @@ void launch_reduce_adam(const std::vector<torch::Tensor>& weights,
                         const c10::optional<torch::Tensor>& gate,
                         hipStream_t stream) {
   const ReduceAdamArgs ra =
-      fill_reduce_adam(weights, biases, totals, ws, stride, n_blocks, m, v,
-                       step, lr, beta1, beta2, eps, weight_decay, step_delta,
-                       gate);
-  launch_mlp_grad_reduce_adam(ra, (long)grand, stream);
+      fill_reduce_adam(weights, biases, n, ws, n.grand, n_blocks, m, v, step,
+                       lr, beta1, beta2, eps, weight_decay, step_delta, gate);
+  launch_mlp_grad_reduce_adam(ra, (long)n.grand, stream);
   HIP_OK(hipGetLastError());
 }
 
-// flat layout of one net's gradient partials: the layers' (od*id + od)
-// segments in layer order; whole_w = floats of the padded whole-net LDS
-// weight image of the fused backward kernels
-struct NetLayout {
-  std::vector<int64_t> totals, layer_off;
-  int64_t grand = 0;
-  size_t whole_w = 0;
-  int max_width = 0;
-};
-
-NetLayout net_layout(const torch::Tensor& x,
-                     const std::vector<torch::Tensor>& weights) {
-  const int L = (int)weights.size();
-  NetLayout n;
-  n.totals.resize(L);
-  n.layer_off.resize(L);
-  n.max_width = (int)x.size(1);
-  for (int l = 0; l < L; ++l) {
-    n.totals[l] = (int64_t)weights[l].size(0) * weights[l].size(1) + weights[l].size(0);
-    n.layer_off[l] = n.grand;
-    n.grand += n.totals[l];
-    n.whole_w += (size_t)weights[l].size(0) * (weights[l].size(1) + 1);
-    n.max_width = std::max(n.max_width, (int)weights[l].size(0));
-  }
-  return n;
-}
-
-// dynamic LDS of the whole-net fused backward: 3 tiles (dZ ping-pong + x),
-// plus one activation tile per layer when the forward runs in the kernel
-size_t fused_bwd_lds(int L, int brows, size_t whole_w, bool fwd_in_kernel) {
-  const size_t act_tiles = (size_t)(fwd_in_kernel ? 3 + L : 3);
-  return (act_tiles * brows * 68 + whole_w) * 4;
-}
-
-// whole-net fused-backward argument block with h[] unset (the in-kernel
-// forward keeps activations in LDS); ws_stride = flat elems per partial row
-MLPBwdArgs fill_bwd_args(const torch::Tensor& x,
-                         const std::vector<torch::Tensor>& weights,
-                         const std::vector<torch::Tensor>& biases,
-                         const std::vector<int64_t>& acts,
-                         const NetLayout& n, int64_t ws_stride) {
-  const int L = (int)weights.size();
-  MLPBwdArgs ba{};
-  ba.n_layers = L;
-  ba.batch = (int)x.size(0);
-  ba.ws_stride = ws_stride;
-  ba.dims[0] = (int)x.size(1);
-  for (int l = 0; l < L; ++l) {
-    ba.w[l] = weights[l].data_ptr<float>();
-    ba.h[l] = nullptr;
-    ba.b[l] = biases[l].data_ptr<float>();
-    ba.dims[l + 1] = (int)weights[l].size(0);
-    ba.acts[l] = (int)acts[l];
-    ba.layer_off[l] = (int)n.layer_off[l];
-  }
-  return ba;
-}
-
-// (ROWS, MAXW) tile selection for the templated MLP kernels.
-// MAXW: smallest instantiated width bound that fits every layer ->
-// smaller LDS footprint, higher per-CU occupancy for the narrow
-// on-policy nets.  ROWS: 32 at large batches fills the 256-CU chip
-// (4000-row batch -> 125 workgroups); 64 otherwise.
-void pick_tile(int batch, int max_width, int* rows, int* maxw) {
-  *maxw = max_width <= 64 ? 64 : 256;
-  // narrow nets: 16-row tiles up to 8K rows (4000-row rollout -> 250
-  // WGs; measured +2.4% over 32-row on the PPO bench — latency hiding
-  // beats weight-staging amortization until the chip is well past
-  // full); 32-row beyond
-  *rows = (*maxw == 256) ? 32 : (batch < 8192 ? 16 : 32);
+// RL_REPLICAS_AMD_MLP_ROWS=16|32|64 (read once): forward row tile override
+int env_mlp_rows() {
   static int env_rows = []() {
     const char* e = getenv("RL_REPLICAS_AMD_MLP_ROWS");
-    return e ? atoi(e) : 0;
+    const int r = e ? atoi(e) : 0;
+    return (r == 16 || r == 32 || r == 64) ? r : 0;
   }();
-  if (env_rows == 16 || env_rows == 32 || env_rows == 64) *rows = env_rows;
-  if (*maxw == 256) *rows = 32;  // only <32,256> is instantiated
+  return env_rows;
 }
 
-#define KCHUNK 64
+// Row tile of the whole-net forward (narrow nets): 16 rows up to 8K rows
+// (4000-row rollout -> 250 WGs; measured +2.4% over 32-row on the PPO
+// bench — latency hiding beats weight-staging amortization until the chip
+// is well past full), 32 beyond.  The override is ignored where its image
+// would not fit the budget (64 rows on a five-layer 64-wide net); the
+// default tile fits every net net_layout admits at MLP_NARROW_WIDTH.
+int fwd_rows(int batch, size_t whole_w) {
+  const int env_rows = env_mlp_rows();
+  if (env_rows != 0 && two_tile_lds(env_rows, whole_w) <= MLP_LDS_BUDGET)
+    return env_rows;
+  return batch < 8192 ? 16 : 32;
+}
 
-// weight-staging mode + dynamic-LDS size for the fused MLP kernels:
-// mode 0 stages the whole net per block (narrow nets), mode 1 stages
-// per-wave W sub-tiles.  act_elems = the two activation ping-pong
-// buffers (fwd) or dz+xt (bwd) — same footprint.
-void pick_wstage(const std::vector<torch::Tensor>& weights, int rows, int maxw,
-                 bool backward_single_layer, int layer, int* mode,
-                 size_t* lds_bytes) {
-  const int ldsw = maxw + 4;
-  size_t act_elems = (size_t)2 * rows * ldsw;
-  size_t whole = 0;
-  if (backward_single_layer) {
-    whole = (size_t)weights[layer].size(0) * (weights[layer].size(1) + 1);
-  } else {
-    for (auto& w : weights) whole += (size_t)w.size(0) * (w.size(1) + 1);
-  }
-  size_t mode0_bytes = (act_elems + whole) * 4;
-  if (mode0_bytes <= 100 * 1024) {
-    *mode = 0;
-    *lds_bytes = mode0_bytes;
-  } else {
-    // wide nets: direct global W reads (mode 2) measure faster than the
-    // serialized per-wave chunk staging (mode 1) at these grid sizes
-    *mode = 2;
-    *lds_bytes = act_elems * 4;
-  }
-  static int env_mode = []() {
-    const char* e = getenv("RL_REPLICAS_AMD_WSTAGE");
-    return e ? atoi(e) : -1;
-  }();
-  if (env_mode == 1 && *mode == 2) {
-    *mode = 1;
-    size_t wv = backward_single_layer ? (size_t)4 * KCHUNK * 18
-                                      : (size_t)4 * 16 * (KCHUNK + 2);
-    *lds_bytes = (act_elems + wv) * 4;
-  }
+// Row tile of the per-layer backward (instantiated at 32 and 64; its
+// single-layer image always fits).  Wide nets: the 2D-grid kernels' 32.
+int bwd_layer_rows(bool wide) {
+  return (!wide && env_mlp_rows() == 64) ? 64 : 32;
 }
 
 }  // namespace
@@ -348,46 +459,32 @@ std::vector<torch::Tensor> mlp_forward(torch::Tensor x,
                                        std::vector<int64_t> acts,
                                        bool save_hidden,
                                        int64_t compute_bf16) {
-  const int L = (int)weights.size();
-  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
-  check_f32_gpu(x, "x");
-  TORCH_CHECK(x.dim() == 2, "x must be 2-D");
+  const NetLayout net = net_layout(x, weights, biases, acts, MLP_MAX_WIDTH);
+  const int L = net.L;
+  // per-layer column-split kernels for wide nets at ANY batch: a whole-net
+  // 256-wide kernel was measured SLOWER at minibatch scale (batch 100 ->
+  // 4 WGs serializing 3 layers each, 800 vs 1232 env-steps/s on the TD3
+  // bench) — concurrency across independent per-layer launches beats
+  // fewer launches here
+  const bool wide = net.max_width > MLP_NARROW_WIDTH;
+  const int batch = (int)x.size(0);
+  const int rows = fwd_rows(batch, net.whole_w);
+  const size_t lds_bytes = two_tile_lds(rows, net.whole_w);
+  TORCH_CHECK(wide || lds_bytes <= MLP_LDS_BUDGET,
+              "net image exceeds the LDS budget");
 
   MLPArgs args{};
-  args.n_layers = L;
-  args.batch = (int)x.size(0);
-  args.dims[0] = (int)x.size(1);
-  for (int l = 0; l < L; ++l) {
-    check_f32_gpu(weights[l], "weight");
-    check_f32_gpu(biases[l], "bias");
-    args.dims[l + 1] = (int)weights[l].size(0);
-    TORCH_CHECK((int)weights[l].size(1) == args.dims[l], "weight shape mismatch");
-    TORCH_CHECK(args.dims[l + 1] <= MLP_MAX_WIDTH && args.dims[l] <= MLP_MAX_WIDTH,
-                "layer width exceeds MLP_MAX_WIDTH");
-    args.w[l] = weights[l].data_ptr<float>();
-    args.b[l] = biases[l].data_ptr<float>();
-    args.acts[l] = (int)acts[l];
-  }
-
-  int max_width = args.dims[0];
-  for (int l = 1; l <= L; ++l) max_width = std::max(max_width, args.dims[l]);
-  int rows, maxw;
-  pick_tile(args.batch, max_width, &rows, &maxw);
+  fill_net(args, net, weights, biases, acts);
+  args.batch = batch;
 
   auto opts = x.options();
-  // per-layer column-split kernels for wide nets at ANY batch: the
-  // whole-net <32,256> path was measured SLOWER at minibatch scale
-  // (batch 100 -> 4 WGs serializing 3 layers each, 800 vs 1232
-  // env-steps/s on the TD3 bench) — concurrency across independent
-  // per-layer launches beats fewer launches here
-  const bool wide = maxw == 256;
   std::vector<torch::Tensor> outs;  // [final, h0..h_{L-2}]
-  torch::Tensor final_out = torch::empty({x.size(0), args.dims[L]}, opts);
+  torch::Tensor final_out = torch::empty({x.size(0), net.dims[L]}, opts);
   outs.push_back(final_out);
   std::vector<torch::Tensor> inter;  // wide path needs intermediates always
   for (int l = 0; l < L - 1; ++l) {
     if (save_hidden || wide) {
-      torch::Tensor h = torch::empty({x.size(0), args.dims[l + 1]}, opts);
+      torch::Tensor h = torch::empty({x.size(0), net.dims[l + 1]}, opts);
       args.h[l] = h.data_ptr<float>();
       if (save_hidden) outs.push_back(h);
       else inter.push_back(h);
@@ -397,25 +494,22 @@ std::vector<torch::Tensor> mlp_forward(torch::Tensor x,
   }
   args.h[L - 1] = final_out.data_ptr<float>();
 
-  if (args.batch > 0) {
+  if (batch > 0) {
     auto stream = current_stream();
     if (wide) {
       // per-layer 2D-grid kernels: column groups spread across blocks
       const float* cur = x.data_ptr<float>();
       for (int l = 0; l < L; ++l) {
-        launch_mlp_layer_fwd_wide(cur, args.w[l], args.b[l], args.h[l],
-                                  args.batch, args.dims[l], args.dims[l + 1],
-                                  args.acts[l], stream);
+        launch_mlp_layer_fwd_wide(cur, args.w[l], args.b[l], args.h[l], batch,
+                                  args.dims[l], args.dims[l + 1], args.acts[l],
+                                  stream);
         HIP_OK(hipGetLastError());
         cur = args.h[l];
       }
     } else {
-      const int n_blocks = (args.batch + rows - 1) / rows;
-      int wmode;
-      size_t lds_bytes;
-      pick_wstage(weights, rows, maxw, false, 0, &wmode, &lds_bytes);
-      launch_mlp_fwd(args, x.data_ptr<float>(), save_hidden ? 1 : 0, rows, maxw,
-                     n_blocks, wmode, lds_bytes, (int)compute_bf16, stream);
+      launch_mlp_fwd(args, x.data_ptr<float>(), save_hidden ? 1 : 0, rows,
+                     (batch + rows - 1) / rows, lds_bytes, (int)compute_bf16,
+                     stream);
       HIP_OK(hipGetLastError());
     }
   }
@@ -438,107 +532,69 @@ std::vector<torch::Tensor> mlp_backward(torch::Tensor grad_out, torch::Tensor x,
                                         c10::optional<torch::Tensor> adam_gate,
                                         bool input_grad_only) {
   const bool fuse_adam = adam_m.has_value();
-  const int L = (int)weights.size();
-  check_f32_gpu(grad_out, "grad_out");
-  check_f32_gpu(x, "x");
+  const NetLayout net = net_layout(x, weights, biases, acts, MLP_MAX_WIDTH);
+  const int L = net.L;
   const int batch = (int)x.size(0);
-  int max_width = (int)x.size(1);
-  for (int l = 0; l < L; ++l)
-    max_width = std::max(max_width, (int)weights[l].size(0));
-  int rows, maxw;
-  pick_tile(batch, max_width, &rows, &maxw);
-  if (rows < 32) rows = 32;  // backward kernels are instantiated at 32/64
-  const int n_blocks = (batch + rows - 1) / rows;
+  check_f32_gpu(grad_out, "grad_out");
+  TORCH_CHECK(grad_out.numel() == (int64_t)batch * net.dims[L],
+              "grad_out shape mismatch");
+  check_saved(net, batch, hidden, final_out);
+  if (fuse_adam) {
+    TORCH_CHECK(adam_v.has_value() && adam_step.has_value(),
+                "adam_m needs adam_v and adam_step");
+    check_adam_state(weights, biases, *adam_m, *adam_v, *adam_step);
+  }
   auto opts = x.options();
   auto stream = current_stream();
-
-  // one workspace: [block][concatenated layer elems] (layer-blind stage-1)
-  std::vector<int64_t> totals(L), layer_off(L);
-  int64_t grand = 0;
-  for (int l = 0; l < L; ++l) {
-    const int out_d = (int)weights[l].size(0);
-    const int in_d = (int)weights[l].size(1);
-    totals[l] = (int64_t)out_d * in_d + out_d;
-    layer_off[l] = grand;
-    grand += totals[l];
-  }
-  // whole-net fused backward for narrow nets when the LDS image fits
-  size_t whole_w = 0;
-  for (auto& w : weights) whole_w += (size_t)w.size(0) * (w.size(1) + 1);
-  const int brows = bwd_fused_rows(batch);
-  const size_t fused_lds = ((size_t)3 * brows * 68 + whole_w) * 4;
-  const bool use_fused_bwd = (maxw == 64) && fused_lds <= 100 * 1024;
-  if (use_fused_bwd) {
-    const int fb = (batch + brows - 1) / brows;
-    torch::Tensor ws = torch::empty({(int64_t)fb, grand}, opts);
-    std::vector<torch::Tensor> dws(L), dbs(L);
-    MLPBwdArgs ba{};
-    ba.n_layers = L;
-    ba.batch = batch;
-    ba.ws_stride = grand;
-    ba.dims[0] = (int)x.size(1);
-    for (int l = 0; l < L; ++l) {
-      ba.w[l] = weights[l].data_ptr<float>();
-      ba.h[l] = (l == L - 1 ? final_out : hidden[l]).data_ptr<float>();
-      ba.dims[l + 1] = (int)weights[l].size(0);
-      ba.acts[l] = (int)acts[l];
-      ba.layer_off[l] = (int)layer_off[l];
-      dws[l] = torch::empty({(int)weights[l].size(0), (int)weights[l].size(1)}, opts);
-      dbs[l] = torch::empty({(int)weights[l].size(0)}, opts);
-    }
-    torch::Tensor dx = torch::empty({batch, x.size(1)}, opts);
-    launch_mlp_bwd_fused(ba, x.data_ptr<float>(),
-                         grad_out.contiguous().data_ptr<float>(),
-                         dx.data_ptr<float>(), ws.data_ptr<float>(), nullptr,
-                         nullptr, fused_lds, fb, (int)compute_bf16, stream,
-                         brows);
-    HIP_OK(hipGetLastError());
-
+  const int64_t grand = net.grand;
+  // weight gradients: consumed on device (fused Adam), not wanted at all
+  // (input_grad_only), or reduced into fresh tensors
+  auto finish = [&](const torch::Tensor& dx, const torch::Tensor& ws,
+                    int n_blocks) -> std::vector<torch::Tensor> {
     if (input_grad_only) return {dx};
     if (fuse_adam) {
-      launch_reduce_adam(weights, biases, totals, ws.data_ptr<float>(), grand,
-                         fb, grand, *adam_m, *adam_v, *adam_step, lr, beta1,
-                         beta2, eps, weight_decay, adam_step_delta, adam_gate,
-                         stream);
+      launch_reduce_adam(weights, biases, net, ws.data_ptr<float>(), n_blocks,
+                         *adam_m, *adam_v, *adam_step, lr, beta1, beta2, eps,
+                         weight_decay, adam_step_delta, adam_gate, stream);
       return {dx};
     }
-    ReduceAllArgs ra{};
-    ra.ws = ws.data_ptr<float>();
-    ra.stride = grand;
-    ra.n_layers = L;
-    ra.n_blocks = fb;
-    for (int l = 0; l < L; ++l) {
-      ra.dw[l] = dws[l].data_ptr<float>();
-      ra.db[l] = dbs[l].data_ptr<float>();
-      ra.total[l] = (int)totals[l];
-      ra.wsize[l] = (int)(weights[l].size(0) * weights[l].size(1));
-    }
-    int rb = (int)std::min<int64_t>(256, (grand + 63) / 64);
-    hipLaunchKernelGGL(mlp_grad_reduce_onepass_f32, dim3(rb), dim3(256), 0,
-                       stream, ra);
+    const GradOut g(net, opts);
+    launch_reduce_all(net, ws.data_ptr<float>(), n_blocks, g, stream);
+    return g.pack(dx);
+  };
+
+  // one workspace: [block][concatenated layer elems] (layer-blind stage-1).
+  // Whole-net fused backward for narrow nets when the LDS image fits
+  if (fused_bwd_fits(net, false)) {
+    const int fb = (batch + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
+    torch::Tensor ws = torch::empty({(int64_t)fb, grand}, opts);
+    MLPBwdArgs ba = fill_bwd_args(x, weights, biases, acts, net, grand);
+    set_saved(ba, net, hidden, final_out);
+    torch::Tensor dx = torch::empty({batch, x.size(1)}, opts);
+    launch_mlp_bwd_fused(ba, x.data_ptr<float>(), grad_out.data_ptr<float>(),
+                         dx.data_ptr<float>(), ws.data_ptr<float>(), nullptr,
+                         nullptr, fused_bwd_lds(net, false), fb,
+                         (int)compute_bf16, stream);
     HIP_OK(hipGetLastError());
-    std::vector<torch::Tensor> out;
-    out.push_back(dx);
-    for (int l = 0; l < L; ++l) out.push_back(dws[l]);
-    for (int l = 0; l < L; ++l) out.push_back(dbs[l]);
-    return out;
+    return finish(dx, ws, fb);
   }
 
+  const bool wide = net.max_width > MLP_NARROW_WIDTH;
+  const int rows = bwd_layer_rows(wide);
+  const int n_blocks = (batch + rows - 1) / rows;
   torch::Tensor ws = torch::empty({(int64_t)n_blocks, grand}, opts);
   float* ws_ptr = ws.data_ptr<float>();
 
-  std::vector<torch::Tensor> dws(L), dbs(L);
-  torch::Tensor dy = grad_out.contiguous();
+  torch::Tensor dy = grad_out;
   torch::Tensor dx;
   for (int l = L - 1; l >= 0; --l) {
-    const int out_d = (int)weights[l].size(0);
-    const int in_d = (int)weights[l].size(1);
+    const int out_d = net.dims[l + 1];
+    const int in_d = net.dims[l];
     torch::Tensor y = (l == L - 1) ? final_out : hidden[l];
     torch::Tensor xin = (l == 0) ? x : hidden[l - 1];
-    dws[l] = torch::empty({out_d, in_d}, opts);
-    dbs[l] = torch::empty({out_d}, opts);
+    float* ws_l = ws_ptr + (long)net.layer_off[l] * n_blocks;
     dx = torch::empty({batch, in_d}, opts);
-    if (maxw == 256) {
+    if (wide) {
       if (input_grad_only) {
         // dgrad chain only (e.g. actor step through a frozen critic:
         // the critic's weight grads would be discarded)
@@ -550,53 +606,24 @@ std::vector<torch::Tensor> mlp_backward(torch::Tensor grad_out, torch::Tensor x,
         // wide layer: 2D-grid dgrad + wgrad kernels
         launch_mlp_bwd_wide(dy.data_ptr<float>(), y.data_ptr<float>(),
                             xin.data_ptr<float>(), weights[l].data_ptr<float>(),
-                            dx.data_ptr<float>(), ws_ptr + (long)layer_off[l] * n_blocks, grand,
-                            batch, out_d, in_d, (int)acts[l], stream);
+                            dx.data_ptr<float>(), ws_l, grand, batch, out_d,
+                            in_d, (int)acts[l], stream);
       }
     } else {
-      int wmode;
-      size_t lds_bytes;
-      pick_wstage(weights, rows, maxw, true, l, &wmode, &lds_bytes);
-      // merged dgrad + wgrad/bias partials in one kernel
+      // merged dgrad + wgrad/bias partials in one kernel: dZ and x tiles
+      // plus this layer's padded weight image
+      const size_t lds_bytes =
+          two_tile_lds(rows, (size_t)out_d * (in_d + 1));
       launch_mlp_bwd_layer(dy.data_ptr<float>(), y.data_ptr<float>(),
                            xin.data_ptr<float>(), weights[l].data_ptr<float>(),
-                           dx.data_ptr<float>(), ws_ptr + (long)layer_off[l] * n_blocks, grand,
-                           batch, out_d, in_d, (int)acts[l], rows, maxw,
-                           n_blocks, wmode, lds_bytes, stream);
+                           dx.data_ptr<float>(), ws_l, grand, batch, out_d,
+                           in_d, (int)acts[l], rows, n_blocks, lds_bytes,
+                           stream);
     }
     HIP_OK(hipGetLastError());
     dy = dx;
   }
-
-  if (input_grad_only) return {dx};
-  if (fuse_adam) {
-    launch_reduce_adam(weights, biases, totals, ws_ptr, grand, n_blocks, grand,
-                       *adam_m, *adam_v, *adam_step, lr, beta1, beta2, eps,
-                       weight_decay, adam_step_delta, adam_gate, stream);
-    return {dx};
-  }
-  // one-pass deterministic reduction over the partial rows
-  ReduceAllArgs ra{};
-  ra.ws = ws_ptr;
-  ra.stride = grand;
-  ra.n_layers = L;
-  ra.n_blocks = n_blocks;
-  for (int l = 0; l < L; ++l) {
-    ra.dw[l] = dws[l].data_ptr<float>();
-    ra.db[l] = dbs[l].data_ptr<float>();
-    ra.total[l] = (int)totals[l];
-    ra.wsize[l] = (int)(weights[l].size(0) * weights[l].size(1));
-  }
-  int rb = (int)std::min<int64_t>(256, (grand + 63) / 64);
-  hipLaunchKernelGGL(mlp_grad_reduce_onepass_f32, dim3(rb), dim3(256), 0,
-                     stream, ra);
-  HIP_OK(hipGetLastError());
-
-  std::vector<torch::Tensor> out;
-  out.push_back(dx);
-  for (int l = 0; l < L; ++l) out.push_back(dws[l]);
-  for (int l = 0; l < L; ++l) out.push_back(dbs[l]);
-  return out;
+  return finish(dx, ws, n_blocks);
 }
 
 // ---------------------------------------------------------------------------
@@ -611,8 +638,8 @@ std::vector<torch::Tensor> gaussian_policy_loss(torch::Tensor mean,
   check_f32_gpu(mean, "mean");
   const int B = (int)mean.size(0);
   const int D = (int)mean.size(1);
-  TORCH_CHECK(D >= 1 && D <= 512,
-              "action dim must be in [1,512] for the fused loss");
+  TORCH_CHECK(D >= 1 && D <= GAUSS_MAX_D, "action dim must be in [1, ",
+              GAUSS_MAX_D, "] for the fused loss");
   auto opts = mean.options();
   auto dmean = torch::empty_like(mean);
   auto dlog_std = torch::empty({D}, opts);
@@ -754,43 +781,41 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
   const bool fuse_adam = adam_m.has_value();
   TORCH_CHECK(!fwd_in_kernel || compute_bf16 == 0,
               "fwd_in_kernel is fp32-only");
-  const int L = (int)weights.size();
-  check_f32_gpu(x, "x");
-  check_f32_gpu(returns, "returns");
-  TORCH_CHECK((int)weights[L - 1].size(0) == 1 && acts[L - 1] == 0,
-              "value_mlp_backward needs a 1-output identity head");
+  const NetLayout net = net_layout(x, weights, biases, acts, MLP_NARROW_WIDTH);
+  const int L = net.L;
   const int batch = (int)x.size(0);
-  const NetLayout net = net_layout(x, weights);
-  TORCH_CHECK(net.max_width <= 64, "value_mlp_backward supports narrow nets only");
-  auto opts = x.options();
-  auto stream = current_stream();
-
-  const std::vector<int64_t>& totals = net.totals;
-  const int64_t grand = net.grand;
-  const int brows = bwd_fused_rows(batch);
-  const size_t fused_lds = fused_bwd_lds(L, brows, net.whole_w, fwd_in_kernel);
-  TORCH_CHECK(fused_lds <= 100 * 1024, "net too large for fused value backward");
-
-  const int fb = (batch + brows - 1) / brows;
-  torch::Tensor ws = torch::empty({(int64_t)fb, grand}, opts);
+  check_f32_gpu(returns, "returns");
+  TORCH_CHECK(returns.numel() == batch, "returns must be [batch]");
+  TORCH_CHECK(net.dims[L] == 1 && acts[L - 1] == 0,
+              "value_mlp_backward needs a 1-output identity head");
+  TORCH_CHECK(fused_bwd_fits(net, fwd_in_kernel),
+              "net too large for fused value backward");
+  // fwd_in_kernel: activations never exist in HBM — the kernel computes
+  // them into LDS (hidden/final_out are ignored)
+  if (!fwd_in_kernel) check_saved(net, batch, hidden, final_out);
+  if (fuse_adam) {
+    TORCH_CHECK(adam_v.has_value() && adam_step.has_value(),
+                "adam_m needs adam_v and adam_step");
+    check_adam_state(weights, biases, *adam_m, *adam_v, *adam_step);
+  }
+  const int fb = (batch + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
   // partials_out: caller-owned slice -> finalize is deferred (the captured
   // value loop batches all iterations' finalizes into one kernel)
   const bool deferred = partials_out.has_value();
-  if (deferred)
-    TORCH_CHECK(partials_out->numel() >= fb && partials_out->is_contiguous(),
-                "partials_out too small");
+  if (deferred) {
+    check_f32_gpu(*partials_out, "partials_out");
+    TORCH_CHECK(partials_out->numel() >= fb, "partials_out too small");
+  }
+  auto opts = x.options();
+  auto stream = current_stream();
+
+  const int64_t grand = net.grand;
+  torch::Tensor ws = torch::empty({(int64_t)fb, grand}, opts);
   torch::Tensor loss_partials = deferred ? *partials_out : torch::empty({fb}, opts);
   torch::Tensor scalars = torch::empty({1}, opts);
-  std::vector<torch::Tensor> dws(L), dbs(L);
+  const GradOut g(net, opts);
   MLPBwdArgs ba = fill_bwd_args(x, weights, biases, acts, net, grand);
-  for (int l = 0; l < L; ++l) {
-    // fwd_in_kernel: activations never exist in HBM — the kernel
-    // computes them into LDS (hidden/final_out are ignored)
-    if (!fwd_in_kernel)
-      ba.h[l] = (l == L - 1 ? final_out : hidden[l]).data_ptr<float>();
-    dws[l] = torch::empty({(int)weights[l].size(0), (int)weights[l].size(1)}, opts);
-    dbs[l] = torch::empty({(int)weights[l].size(0)}, opts);
-  }
+  if (!fwd_in_kernel) set_saved(ba, net, hidden, final_out);
   // the fused-Adam mode consumes the gradient on device and nobody reads
   // the input gradient: skip computing it and return an empty dx slot
   torch::Tensor dx = fuse_adam ? torch::empty({0}, opts)
@@ -798,32 +823,18 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
   launch_mlp_bwd_fused(ba, x.data_ptr<float>(), nullptr,
                        fuse_adam ? nullptr : dx.data_ptr<float>(),
                        ws.data_ptr<float>(), returns.data_ptr<float>(),
-                       loss_partials.data_ptr<float>(), fused_lds, fb,
-                       (int)compute_bf16, stream, brows, fwd_in_kernel ? 1 : 0,
+                       loss_partials.data_ptr<float>(),
+                       fused_bwd_lds(net, fwd_in_kernel), fb,
+                       (int)compute_bf16, stream, fwd_in_kernel ? 1 : 0,
                        GaussSeedArgs{}, fuse_adam ? 0 : 1);
   HIP_OK(hipGetLastError());
 
   if (fuse_adam) {
-    launch_reduce_adam(weights, biases, totals, ws.data_ptr<float>(), grand,
-                       fb, grand, *adam_m, *adam_v, *adam_step, lr, beta1,
-                       beta2, eps, weight_decay, adam_step_delta,
-                       c10::nullopt, stream);
+    launch_reduce_adam(weights, biases, net, ws.data_ptr<float>(), fb,
+                       *adam_m, *adam_v, *adam_step, lr, beta1, beta2, eps,
+                       weight_decay, adam_step_delta, c10::nullopt, stream);
   } else {
-    ReduceAllArgs ra{};
-    ra.ws = ws.data_ptr<float>();
-    ra.stride = grand;
-    ra.n_layers = L;
-    ra.n_blocks = fb;
-    for (int l = 0; l < L; ++l) {
-      ra.dw[l] = dws[l].data_ptr<float>();
-      ra.db[l] = dbs[l].data_ptr<float>();
-      ra.total[l] = (int)totals[l];
-      ra.wsize[l] = (int)(weights[l].size(0) * weights[l].size(1));
-    }
-    int rb = (int)std::min<int64_t>(256, (grand + 63) / 64);
-    hipLaunchKernelGGL(mlp_grad_reduce_onepass_f32, dim3(rb), dim3(256), 0,
-                       stream, ra);
-    HIP_OK(hipGetLastError());
+    launch_reduce_all(net, ws.data_ptr<float>(), fb, g, stream);
   }
   if (!deferred) {
     // loss = sum of the per-block partials (fixed order)
@@ -833,10 +844,7 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
     HIP_OK(hipGetLastError());
   }
 
-  std::vector<torch::Tensor> out;
-  out.push_back(dx);
-  for (int l = 0; l < L; ++l) out.push_back(dws[l]);
-  for (int l = 0; l < L; ++l) out.push_back(dbs[l]);
+  std::vector<torch::Tensor> out = g.pack(dx);
   out.push_back(scalars);
   return out;
 }
@@ -1288,12 +1296,49 @@ struct PolicyIterBlocks {
   ReduceAdamArgs ra;
   torch::Tensor ws, loss_partials, kl_partials;
   size_t fused_lds;
-  int fb, brows;
+  int fb;
   int64_t grand_ls;
 };
 
-PolicyIterBlocks build_policy_iter(
+// every check of one Gaussian-PPO policy iteration's arguments
+NetLayout check_policy_iter(
     const torch::Tensor& x, const std::vector<torch::Tensor>& weights,
+    const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
+    const torch::Tensor& actions, const torch::Tensor& old_logp,
+    const torch::Tensor& advantages, const torch::Tensor& log_std,
+    const std::vector<torch::Tensor>& adam_m,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& ls_m,
+    const torch::Tensor& ls_v, const torch::Tensor& adam_step,
+    const torch::Tensor& gate, const torch::Tensor& kl_final,
+    const torch::Tensor& iters_done, const torch::Tensor& loss_out) {
+  // one slot of the fixed argument arrays goes to the log_std pseudo-layer
+  const NetLayout net =
+      net_layout(x, weights, biases, acts, MLP_NARROW_WIDTH, 1);
+  const int64_t batch = x.size(0);
+  const int D = net.dims[net.L];
+  TORCH_CHECK(acts[net.L - 1] == 0, "needs an identity head");
+  TORCH_CHECK(fused_bwd_fits(net, true), "net too large for the fused iter");
+  check_f32_gpu(actions, "actions");
+  check_f32_gpu(old_logp, "old_logp");
+  check_f32_gpu(advantages, "advantages");
+  TORCH_CHECK(actions.numel() == batch * D && old_logp.numel() == batch &&
+                  advantages.numel() == batch,
+              "actions/old_logp/advantages must be [batch, D]/[batch]/[batch]");
+  for (const torch::Tensor* t : {&log_std, &ls_m, &ls_v}) {
+    check_f32_gpu(*t, "log_std and its adam state");
+    TORCH_CHECK(t->numel() == D, "log_std and its adam state must be [D]");
+  }
+  check_adam_state(weights, biases, adam_m, adam_v, adam_step);
+  for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
+    check_f32_gpu(*t, "gate/kl_final/iters_done/loss_out");
+    TORCH_CHECK(t->numel() == 1, "gate bookkeeping scalars must have 1 element");
+  }
+  return net;
+}
+
+PolicyIterBlocks build_policy_iter(
+    const NetLayout& net, const torch::Tensor& x,
+    const std::vector<torch::Tensor>& weights,
     const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
     const torch::Tensor& actions, const torch::Tensor& old_logp,
     const torch::Tensor& advantages, const torch::Tensor& log_std, double clip,
@@ -1304,23 +1349,15 @@ PolicyIterBlocks build_policy_iter(
     double step_delta, const torch::Tensor& gate, const torch::Tensor& kl_final,
     const torch::Tensor& iters_done, double thr, const torch::Tensor& loss_out,
     bool first_iter) {
-  const int L = (int)weights.size();
-  check_f32_gpu(x, "x");
+  const int L = net.L;
   const int batch = (int)x.size(0);
-  const int D = (int)weights[L - 1].size(0);
-  TORCH_CHECK(acts[L - 1] == 0, "needs an identity head");
-  TORCH_CHECK(L + 1 <= MLP_MAX_LAYERS, "too many layers for the log_std slot");
-  TORCH_CHECK(D <= 64, "action dim must fit one LDS row");
-  const NetLayout net = net_layout(x, weights);
-  TORCH_CHECK(net.max_width <= 64, "narrow nets only");
+  const int D = net.dims[L];
   auto opts = x.options();
 
   PolicyIterBlocks pb;
   pb.grand_ls = net.grand + D;  // + dlog_std pseudo-layer
-  pb.brows = bwd_fused_rows(batch);
-  pb.fused_lds = fused_bwd_lds(L, pb.brows, net.whole_w, true);
-  TORCH_CHECK(pb.fused_lds <= 100 * 1024, "net too large for the fused iter");
-  pb.fb = (batch + pb.brows - 1) / pb.brows;
+  pb.fused_lds = fused_bwd_lds(net, true);
+  pb.fb = (batch + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
 
   pb.ws = torch::empty({(int64_t)pb.fb, pb.grand_ls}, opts);
   pb.loss_partials = torch::empty({pb.fb}, opts);
@@ -1340,12 +1377,8 @@ PolicyIterBlocks build_policy_iter(
   // gates and its loss partials are always read, so it always runs.
   ga.skip_gate = first_iter ? nullptr : gate.data_ptr<float>();
 
-  for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
-    check_f32_gpu(*t, "gate/kl_final/iters_done/loss_out");
-    TORCH_CHECK(t->numel() == 1, "gate bookkeeping scalars must have 1 element");
-  }
   ReduceAdamArgs& ra = pb.ra;
-  ra = fill_reduce_adam(weights, biases, net.totals, pb.ws.data_ptr<float>(),
+  ra = fill_reduce_adam(weights, biases, net, pb.ws.data_ptr<float>(),
                         pb.grand_ls, pb.fb, adam_m, adam_v, adam_step, lr,
                         beta1, beta2, eps, weight_decay, step_delta, gate);
   ra.n_layers = L + 1;
@@ -1384,9 +1417,12 @@ torch::Tensor gaussian_ppo_policy_iter(
     double weight_decay, double step_delta, torch::Tensor gate,
     torch::Tensor kl_final, torch::Tensor iters_done, double thr,
     torch::Tensor loss_out, bool first_iter) {
+  const NetLayout net = check_policy_iter(
+      x, weights, biases, acts, actions, old_logp, advantages, log_std, adam_m,
+      adam_v, ls_m, ls_v, adam_step, gate, kl_final, iters_done, loss_out);
   const PolicyIterBlocks pb = build_policy_iter(
-      x, weights, biases, acts, actions, old_logp, advantages, log_std, clip,
-      adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
+      net, x, weights, biases, acts, actions, old_logp, advantages, log_std,
+      clip, adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
       weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
       first_iter);
   auto stream = current_stream();
@@ -1394,7 +1430,7 @@ torch::Tensor gaussian_ppo_policy_iter(
   launch_mlp_bwd_fused(pb.ba, x.data_ptr<float>(), nullptr, nullptr,
                        pb.ws.data_ptr<float>(), nullptr,
                        pb.loss_partials.data_ptr<float>(), pb.fused_lds, pb.fb,
-                       0, stream, pb.brows, 1, pb.ga, 0);
+                       0, stream, 1, pb.ga, 0);
   HIP_OK(hipGetLastError());
   launch_mlp_grad_reduce_adam(pb.ra, (long)pb.grand_ls, stream);
   HIP_OK(hipGetLastError());
@@ -1415,15 +1451,13 @@ bool ppo_twin_uses_shaped(std::vector<int64_t> p_dims,
                           std::vector<int64_t> v_dims, int64_t batch) {
   const char* e = getenv("RL_REPLICAS_AMD_TWIN_SHAPED");
   if (e != nullptr && e[0] == '0' && e[1] == '\0') return false;
-  return bwd_fused_rows((int)batch) == 32 && twin_shaped_net_ok(p_dims, 16) &&
-         twin_shaped_net_ok(v_dims, 1) && p_dims[0] == v_dims[0];
+  static_assert(BWD_FUSED_ROWS == 32, "the shaped twin kernel has 32-row blocks");
+  return twin_shaped_net_ok(p_dims, 16) && twin_shaped_net_ok(v_dims, 1) &&
+         p_dims[0] == v_dims[0];
 }
 
-static std::vector<int64_t> net_dims(const torch::Tensor& x,
-                                     const std::vector<torch::Tensor>& weights) {
-  std::vector<int64_t> d{x.size(1)};
-  for (const torch::Tensor& w : weights) d.push_back(w.size(0));
-  return d;
+static std::vector<int64_t> net_dims(const NetLayout& n) {
+  return std::vector<int64_t>(n.dims, n.dims + n.L + 1);
 }
 
 // Policy iteration i and value iteration i of one PPO epoch in the SAME
@@ -1453,28 +1487,36 @@ void gaussian_ppo_value_twin_iter(
     std::vector<torch::Tensor> v_adam_v, torch::Tensor v_adam_step,
     double v_lr, double v_beta1, double v_beta2, double v_eps,
     double v_weight_decay, double v_step_delta) {
+  const NetLayout net = check_policy_iter(
+      x, weights, biases, acts, actions, old_logp, advantages, log_std, adam_m,
+      adam_v, ls_m, ls_v, adam_step, gate, kl_final, iters_done, loss_out);
   TORCH_CHECK(v_x.data_ptr() == x.data_ptr() && v_x.sizes() == x.sizes(),
               "the twin iteration needs the same x for both nets");
+  const NetLayout vnet =
+      net_layout(x, v_weights, v_biases, v_acts, MLP_NARROW_WIDTH);
+  const int fb = ((int)x.size(0) + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
+  check_f32_gpu(returns, "returns");
+  TORCH_CHECK(returns.numel() == x.size(0), "returns must be [batch]");
+  TORCH_CHECK(vnet.dims[vnet.L] == 1 && v_acts[vnet.L - 1] == 0,
+              "the value half needs a 1-output identity head");
+  TORCH_CHECK(fused_bwd_fits(vnet, true),
+              "value net too large for the fused iter");
+  check_adam_state(v_weights, v_biases, v_adam_m, v_adam_v, v_adam_step);
+  check_f32_gpu(v_partials_out, "v_partials_out");
+  TORCH_CHECK(v_partials_out.numel() >= fb, "v_partials_out too small");
+  TORCH_CHECK(mlp_reduce_adam_is_staged(fb, (long)(net.grand + net.dims[net.L])) &&
+                  mlp_reduce_adam_is_staged(fb, (long)vnet.grand),
+              "the twin reduce needs both nets on the staged reduce");
+  const bool shaped =
+      ppo_twin_uses_shaped(net_dims(net), net_dims(vnet), x.size(0));
+  TORCH_CHECK(!shaped || mlp_bwd_fused_shaped_lds(net.dims[0]) <= 80 * 1024,
+              "shaped twin kernel over its LDS budget");
+
   const PolicyIterBlocks pb = build_policy_iter(
-      x, weights, biases, acts, actions, old_logp, advantages, log_std, clip,
-      adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
+      net, x, weights, biases, acts, actions, old_logp, advantages, log_std,
+      clip, adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
       weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
       first_iter);
-
-  const int VL = (int)v_weights.size();
-  check_f32_gpu(returns, "returns");
-  TORCH_CHECK((int)returns.numel() == (int)x.size(0), "returns must be [batch]");
-  TORCH_CHECK((int)v_weights[VL - 1].size(0) == 1 && v_acts[VL - 1] == 0,
-              "the value half needs a 1-output identity head");
-  const NetLayout vnet = net_layout(x, v_weights);
-  TORCH_CHECK(vnet.max_width <= 64, "narrow nets only");
-  const size_t v_lds = fused_bwd_lds(VL, pb.brows, vnet.whole_w, true);
-  TORCH_CHECK(v_lds <= 100 * 1024, "value net too large for the fused iter");
-  check_f32_gpu(v_partials_out, "v_partials_out");
-  TORCH_CHECK(v_partials_out.numel() >= pb.fb, "v_partials_out too small");
-  TORCH_CHECK(mlp_reduce_adam_is_staged(pb.fb, (long)pb.grand_ls) &&
-                  mlp_reduce_adam_is_staged(pb.fb, (long)vnet.grand),
-              "the twin reduce needs both nets on the staged reduce");
   torch::Tensor v_ws = torch::empty({(int64_t)pb.fb, vnet.grand}, x.options());
 
   MLPBwdTwinArgs ta{};
@@ -1488,20 +1530,17 @@ void gaussian_ppo_value_twin_iter(
   ta.val_loss_partials = v_partials_out.data_ptr<float>();
   ta.x = x.data_ptr<float>();
   auto stream = current_stream();
-  if (ppo_twin_uses_shaped(net_dims(x, weights), net_dims(x, v_weights),
-                           x.size(0))) {
-    TORCH_CHECK(mlp_bwd_fused_shaped_lds((int)x.size(1)) <= 80 * 1024,
-                "shaped twin kernel over its LDS budget");
+  if (shaped) {
     launch_mlp_bwd_fused_twin_shaped(ta, pb.fb, stream);
   } else {
-    launch_mlp_bwd_fused_twin(ta, std::max(pb.fused_lds, v_lds), pb.fb,
-                              pb.brows, stream);
+    launch_mlp_bwd_fused_twin(
+        ta, std::max(pb.fused_lds, fused_bwd_lds(vnet, true)), pb.fb, stream);
   }
   HIP_OK(hipGetLastError());
 
   const ReduceAdamArgs vra = fill_reduce_adam(
-      v_weights, v_biases, vnet.totals, v_ws.data_ptr<float>(), vnet.grand,
-      pb.fb, v_adam_m, v_adam_v, v_adam_step, v_lr, v_beta1, v_beta2, v_eps,
+      v_weights, v_biases, vnet, v_ws.data_ptr<float>(), vnet.grand, pb.fb,
+      v_adam_m, v_adam_v, v_adam_step, v_lr, v_beta1, v_beta2, v_eps,
       v_weight_decay, v_step_delta, c10::nullopt);
   launch_mlp_grad_reduce_adam_twin(pb.ra, (long)pb.grand_ls, vra,
                                    (long)vnet.grand, stream);
@@ -1517,18 +1556,11 @@ void counter_add_(torch::Tensor ctr, int64_t delta) {
   HIP_OK(hipGetLastError());
 }
 
-// LDS budget of the persistent rollout kernel: the same 100 KiB bound the
-// whole-net-staged MLP kernels use (pick_wstage)
-#define ROLLOUT_FUSED_MAX_LDS (100 * 1024)
-
 // dims = [O, hidden..., A] of the policy net
 int64_t ppo_rollout_fused_lds_bytes_py(std::vector<int64_t> dims, int64_t O,
                                        int64_t A) {
-  const int L = (int)dims.size() - 1;
-  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
-  int d[MLP_MAX_LAYERS + 1];
-  for (int l = 0; l <= L; ++l) d[l] = (int)dims[l];
-  return (int64_t)ppo_rollout_fused_lds_bytes(d, L, (int)O, (int)A);
+  const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
+  return (int64_t)ppo_rollout_fused_lds_bytes(n.dims, n.L, (int)O, (int)A);
 }
 
 // whole-epoch rollout in one launch (rollout_fused_kernels.hip): writes
@@ -1543,10 +1575,6 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
                        torch::Tensor ctr, torch::Tensor obs_full,
                        torch::Tensor act_buf, torch::Tensor rew_buf,
                        torch::Tensor cut_final) {
-  const int L = (int)weights.size();
-  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
-  TORCH_CHECK((int)biases.size() == L && (int)acts.size() == L,
-              "weights/biases/acts length mismatch");
   check_f32_gpu(obs_full, "obs_full");
   check_f32_gpu(act_buf, "act_buf");
   check_f32_gpu(rew_buf, "rew_buf");
@@ -1573,23 +1601,11 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
                   envB.dim() == 2 && envB.size(0) == a.A && envB.size(1) == a.O &&
                   envw.numel() == a.O,
               "env matrices must be A[O,O], B[A,O], w[O]");
-  a.n_layers = L;
-  a.dims[0] = a.O;
-  for (int l = 0; l < L; ++l) {
-    check_f32_gpu(weights[l], "weight");
-    check_f32_gpu(biases[l], "bias");
-    a.dims[l + 1] = (int)weights[l].size(0);
-    TORCH_CHECK(weights[l].dim() == 2 && (int)weights[l].size(1) == a.dims[l],
-                "weight shape mismatch");
-    TORCH_CHECK((int)biases[l].numel() == a.dims[l + 1], "bias shape mismatch");
-    TORCH_CHECK(a.dims[l + 1] <= ROLLOUT_MAX_WIDTH,
-                "ppo_rollout_fused: layer width must be <= ", ROLLOUT_MAX_WIDTH);
-    a.w[l] = weights[l].data_ptr<float>();
-    a.b[l] = biases[l].data_ptr<float>();
-    a.acts[l] = (int)acts[l];
-  }
+  const NetLayout net = net_layout(a.O, weights, biases, acts, ROLLOUT_MAX_WIDTH);
+  fill_net(a, net, weights, biases, acts);
+  const int L = net.L;
   TORCH_CHECK(a.dims[L] == a.A, "policy head width must equal the action dim");
-  TORCH_CHECK(ppo_rollout_fused_lds_bytes(a.dims, L, a.O, a.A) <= ROLLOUT_FUSED_MAX_LDS,
+  TORCH_CHECK(ppo_rollout_fused_lds_bytes(a.dims, L, a.O, a.A) <= MLP_LDS_BUDGET,
               "ppo_rollout_fused: net + env image exceeds the LDS budget");
   a.n_cuts = (int)cuts.size();
   TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "ppo_rollout_fused: too many cuts");
@@ -1623,11 +1639,8 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
 
 // dims = [4, hidden..., n_act] of the policy net
 int64_t cartpole_rollout_fused_lds_bytes_py(std::vector<int64_t> dims) {
-  const int L = (int)dims.size() - 1;
-  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
-  int d[MLP_MAX_LAYERS + 1];
-  for (int l = 0; l <= L; ++l) d[l] = (int)dims[l];
-  return (int64_t)cartpole_rollout_fused_lds_bytes(d, L);
+  const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
+  return (int64_t)cartpole_rollout_fused_lds_bytes(n.dims, n.L);
 }
 
 // whole-epoch CartPole rollout in one launch (cartpole_rollout_kernels.hip):
@@ -1642,10 +1655,8 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
                             torch::Tensor obs_full, torch::Tensor final_obs,
                             torch::Tensor act_buf, torch::Tensor rew_buf,
                             torch::Tensor done_buf) {
-  const int L = (int)weights.size();
-  TORCH_CHECK(L >= 1 && L <= MLP_MAX_LAYERS, "unsupported layer count ", L);
-  TORCH_CHECK((int)biases.size() == L && (int)acts.size() == L,
-              "weights/biases/acts length mismatch");
+  const NetLayout net = net_layout(4, weights, biases, acts, ROLLOUT_MAX_WIDTH);
+  const int L = net.L;
   CartPoleRolloutArgs a{};
   a.N = check_cartpole_carry(state, elapsed);
   check_f32_gpu(obs_full, "obs_full");
@@ -1658,22 +1669,7 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
   check_out(act_buf, torch::kInt64, SN, "act_buf");
   check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
   check_out(done_buf, torch::kUInt8, SN, "done_buf");
-  a.n_layers = L;
-  a.dims[0] = 4;
-  for (int l = 0; l < L; ++l) {
-    check_f32_gpu(weights[l], "weight");
-    check_f32_gpu(biases[l], "bias");
-    a.dims[l + 1] = (int)weights[l].size(0);
-    TORCH_CHECK(weights[l].dim() == 2 && (int)weights[l].size(1) == a.dims[l],
-                "weight shape mismatch");
-    TORCH_CHECK((int)biases[l].numel() == a.dims[l + 1], "bias shape mismatch");
-    TORCH_CHECK(a.dims[l + 1] >= 1 && a.dims[l + 1] <= ROLLOUT_MAX_WIDTH,
-                "cartpole_rollout_fused: layer width must be in [1, ",
-                ROLLOUT_MAX_WIDTH, "]");
-    a.w[l] = weights[l].data_ptr<float>();
-    a.b[l] = biases[l].data_ptr<float>();
-    a.acts[l] = (int)acts[l];
-  }
+  fill_net(a, net, weights, biases, acts);
   TORCH_CHECK(cartpole_rollout_fused_lds_bytes(a.dims, L) <= CARTPOLE_ROLLOUT_MAX_LDS,
               "cartpole_rollout_fused: net image exceeds the LDS budget");
   a.state = state.data_ptr<double>();
@@ -1732,10 +1728,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ppo_rollout_fused_limits",
         []() {
           return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
-                                      ROLLOUT_MAX_CUTS, ROLLOUT_FUSED_MAX_LDS};
+                                      ROLLOUT_MAX_CUTS, (int64_t)MLP_LDS_BUDGET};
         },
         "(max layers, max width / obs dim, max cuts, LDS budget in bytes) of "
         "ppo_rollout_fused");
+  m.def("fused_mlp_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH,
+                                      MLP_NARROW_WIDTH, GAUSS_MAX_D};
+        },
+        "(max layers, max width, max width of the whole-net LDS-image "
+        "kernels = max action dim of the fused policy iteration, max action "
+        "dim of the Gaussian loss kernel)");
+  m.def("fused_bwd_fits",
+        [](std::vector<int64_t> dims, int64_t reserve) {
+          try {
+            const NetLayout n = net_layout(dims, MLP_MAX_WIDTH, (int)reserve);
+            return std::vector<bool>{fused_bwd_fits(n, false),
+                                     fused_bwd_fits(n, true)};
+          } catch (const c10::Error&) {  // no net the bindings take at all
+            return std::vector<bool>{false, false};
+          }
+        },
+        "whether the whole-net fused backward takes a net [in, ..., out]: "
+        "(with a separate forward, with the forward in the kernel); reserve "
+        "= argument-block slots kept free (1 for the log_std pseudo-layer)",
+        py::arg("dims"), py::arg("reserve") = 0);
   m.def("mlp_forward", &mlp_forward, "fused MLP forward (gfx950)",
         py::arg("x"), py::arg("weights"), py::arg("biases"), py::arg("acts"),
         py::arg("save_hidden"), py::arg("compute_bf16") = 0);
@@ -1760,8 +1778,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("adam_step_delta") = 0.0, py::arg("fwd_in_kernel") = false);
   m.def("value_loss_partials_blocks",
         [](int64_t batch) {
-          const int brows = bwd_fused_rows((int)batch);
-          return (batch + brows - 1) / brows;
+          return (batch + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
         },
         "partials row length used by value_mlp_backward");
   m.def("value_loss_finalize", &value_loss_finalize,

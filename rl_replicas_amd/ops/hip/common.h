@@ -66,11 +66,18 @@ DEV_INLINE float wave_reduce_sum(float v) {
   return v;
 }
 
-// Fused-MLP static limits (mirrored in ops/fused_mlp.py)
+// Fused-MLP static limits.  Python reads them from the extension
+// (fused_mlp_limits); ops/fused_mlp.py keeps MAX_LAYERS / MAX_WIDTH for
+// hosts without it, and a GPU test holds the two equal.
 #define MLP_MAX_LAYERS 5
 #define MLP_MAX_WIDTH 256
-#define MLP_ROWS 64            // rows per workgroup (4 waves x 16)
-#define MLP_LDSW (MLP_MAX_WIDTH + 4)  // padded LDS row stride (bank spread)
+// widest layer of the kernels that keep a whole net's padded weight image
+// in LDS beside [rows][MLP_NARROW_WIDTH + 4] activation tiles
+#define MLP_NARROW_WIDTH 64
+// dynamic-LDS budget per workgroup of those kernels and of the persistent
+// rollout kernel: 100 of the CU's 160 KiB
+#define MLP_LDS_BUDGET ((size_t)100 * 1024)
+#define GAUSS_MAX_D 512  // Gaussian loss kernels' LDS sigma table bound
 
 // kernel-argument block for the fused MLP kernels (passed by value)
 struct MLPArgs {

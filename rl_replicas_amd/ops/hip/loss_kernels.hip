@@ -45,7 +45,6 @@ DEV_INLINE float block_sum(float v, float* red /*[LOSS_THREADS/WAVE]*/) {
 // ---------------------------------------------------------------------------
 #define LOSS_BLOCKS 32
 #define LOSS_P_THREADS 256
-#define GAUSS_MAX_D 512  // generic-D kernel's LDS sigma table bound
 
 template <int DT>
 __global__ __launch_bounds__(LOSS_P_THREADS) void gaussian_policy_loss_bwd_t(

@@ -11,14 +11,12 @@
 //
 // Weight access is the latency hazard at these sizes (a scattered
 // per-lane W read per MFMA serializes on L2 latency when the grid is
-// small), so weights are staged through LDS:
-//   mode 0 (narrow nets): the ENTIRE net's weights are staged once per
-//     block into a padded LDS image ([out][(in+1)] per layer -> odd row
-//     stride, bank-conflict-free for both W and W^T reads);
-//   mode 1 (wide nets): each wave stages per-(output-tile, K-chunk)
-//     sub-tiles of W into its private LDS slice, synchronized with
-//     wave-local lgkmcnt waits (no cross-wave barriers).
-// The host picks the mode from the LDS budget (dynamic shared memory).
+// small), so the narrow kernels (widths <= 64) stage weights through LDS:
+// the ENTIRE net's weights (one layer's, in the per-layer backward) are
+// staged once per block into a padded LDS image ([out][(in+1)] per layer
+// -> odd row stride, bank-conflict-free for both W and W^T reads).  The
+// host sizes the dynamic LDS and admits only nets whose image fits its
+// budget; wider nets run the per-layer column-split kernels further down.
 //
 // Backward = ONE merged kernel per layer (dgrad + wgrad/bias partials
 // sharing the staged dZ tile) + a TWO-STAGE deterministic partial
@@ -65,42 +63,31 @@ DEV_INLINE void stage_weights_block(const float* __restrict__ W, float* wlds,
   }
 }
 
-// wave-local LDS write->read ordering (all writers are this wave's lanes)
-DEV_INLINE void wave_lds_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-#define KCHUNK 64  // K-chunk depth for mode-1 weight staging
-
 // ---------------------------------------------------------------------------
 // fused forward
 // ---------------------------------------------------------------------------
 template <int ROWS, int MAXW, bool BF16 = false>
 __global__ __launch_bounds__(256) void fused_mlp_fwd_f32_t(
-    MLPArgs args, const float* __restrict__ x, int save_hidden, int wstage_mode) {
+    MLPArgs args, const float* __restrict__ x, int save_hidden) {
   constexpr int LDSW = MAXW + 4;
   constexpr int RT = ROWS / 16;        // row tiles per block
   constexpr int JT_STRIDE = 4 / RT;    // waves sharing one row tile
   extern __shared__ float smem[];
   float* const buf0 = smem;
   float* const buf1 = smem + ROWS * LDSW;
-  float* wlds = smem + 2 * ROWS * LDSW;  // mode 0: whole net; mode 1: per-wave
+  float* wlds = smem + 2 * ROWS * LDSW;  // whole-net weight image
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int row0 = blockIdx.x * ROWS;
   const int wr0 = (wave % RT) * 16;
   const int jt0 = (wave / RT) * 16;
-  // mode-1 per-wave W slice: [16][KCHUNK+2]
-  float* wv = wlds + wave * 16 * (KCHUNK + 2);
 
   load_tile<LDSW>(x, buf0, row0, args.batch, args.dims[0], tid, ROWS);
-  if (wstage_mode == 0) {
-    int off = 0;
-    for (int l = 0; l < args.n_layers; ++l) {
-      stage_weights_block(args.w[l], wlds + off, args.dims[l + 1], args.dims[l], tid);
-      off += args.dims[l + 1] * (args.dims[l] + 1);
-    }
+  int off = 0;
+  for (int l = 0; l < args.n_layers; ++l) {
+    stage_weights_block(args.w[l], wlds + off, args.dims[l + 1], args.dims[l], tid);
+    off += args.dims[l + 1] * (args.dims[l] + 1);
   }
   __syncthreads();
 
@@ -111,50 +98,19 @@ __global__ __launch_bounds__(256) void fused_mlp_fwd_f32_t(
   for (int l = 0; l < args.n_layers; ++l) {
     const int in_d = args.dims[l];
     const int out_d = args.dims[l + 1];
-    const float* W = args.w[l];
     const float* B = args.b[l];
     const int act = args.acts[l];
     const int nxt = cur ^ 1;
     const float* buf_in = (cur == 0) ? buf0 : buf1;
     float* buf_out = (cur == 0) ? buf1 : buf0;
-    const int wrow = in_d + 1;  // mode-0 padded W row stride
+    const int wrow = in_d + 1;  // padded W row stride
 
     for (int jt = jt0; jt < out_d; jt += 16 * JT_STRIDE) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       const int j = jt + i;
       const bool jok = j < out_d;
-      if (wstage_mode == 0) {
-        // shared with the persistent rollout kernel (rollout_steps.h)
-        acc = mlp_fwd_tile_lds<LDSW, BF16>(buf_in, wlds + woff, wrow, in_d,
-                                           wr0 + i, k, j, jok);
-      } else if (wstage_mode == 2) {
-        // direct global W reads (wide nets at large grids: the L2
-        // misses hide behind cross-wave parallelism)
-        for (int k0 = 0; k0 < in_d; k0 += 4) {
-          const int kk = k0 + k;
-          float a = (kk < in_d) ? buf_in[(wr0 + i) * LDSW + kk] : 0.f;
-          float bv = (jok && kk < in_d) ? W[(long)j * in_d + kk] : 0.f;
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-        }
-      } else {
-        // per-wave staged K-chunks of W[jt..jt+16)[c0..c0+KCHUNK)
-        for (int c0 = 0; c0 < in_d; c0 += KCHUNK) {
-          const int clen = min(KCHUNK, in_d - c0);
-          for (int idx = lane; idx < 16 * clen; idx += 64) {
-            int r = idx / clen, c = idx % clen;
-            float v = (jt + r < out_d) ? W[(long)(jt + r) * in_d + c0 + c] : 0.f;
-            wv[r * (KCHUNK + 2) + c] = v;
-          }
-          wave_lds_fence();
-          for (int k0 = 0; k0 < clen; k0 += 4) {
-            const int kk = k0 + k;
-            float a = (kk < clen) ? buf_in[(wr0 + i) * LDSW + c0 + kk] : 0.f;
-            float bv = (kk < clen) ? wv[i * (KCHUNK + 2) + kk] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-          }
-          wave_lds_fence();  // reads done before next chunk overwrites
-        }
-      }
+      // shared with the persistent rollout kernel (rollout_steps.h)
+      const f32x4 acc = mlp_fwd_tile_lds<LDSW, BF16>(buf_in, wlds + woff, wrow,
+                                                     in_d, wr0 + i, k, j, jok);
       mlp_fwd_tile_epilogue<LDSW>(acc, B, act, j, jok, wr0, lane, buf_out);
     }
     __syncthreads();
@@ -182,7 +138,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
     const float* __restrict__ dy, const float* __restrict__ y,
     const float* __restrict__ xin, const float* __restrict__ W,
     float* __restrict__ dx, float* __restrict__ workspace, long ws_stride,
-    int batch, int out_d, int in_d, int act, int wstage_mode) {
+    int batch, int out_d, int in_d, int act) {
   constexpr int LDSW = MAXW + 4;
   constexpr int RT = ROWS / 16;
   constexpr int JT_STRIDE = 4 / RT;
@@ -196,7 +152,6 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
   const int row0 = blockIdx.x * ROWS;
   const int wr0 = (wave % RT) * 16;
   const int jt0 = (wave / RT) * 16;
-  float* wv = wlds + wave * KCHUNK * 18;  // mode-1 slice: [KCHUNK][16+2]
   // element-major workspace (ws[elem][block]): the latency-bound reduce
   // reads each element's partials CONTIGUOUSLY; writers scatter instead
   // (stores don't stall)
@@ -214,9 +169,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
     dz[r * LDSW + c] = v;
   }
   load_tile<LDSW>(xin, xt, row0, batch, in_d, tid, ROWS);
-  if (wstage_mode == 0) {
-    stage_weights_block(W, wlds, out_d, in_d, tid);
-  }
+  stage_weights_block(W, wlds, out_d, in_d, tid);
   __syncthreads();
 
   const int i = lane & 15;
@@ -228,38 +181,11 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const int j = jt + i;
     const bool jok = j < in_d;
-    if (wstage_mode == 0) {
-      for (int k0 = 0; k0 < out_d; k0 += 4) {
-        const int kk = k0 + k;
-        float a = (kk < out_d) ? dz[(wr0 + i) * LDSW + kk] : 0.f;
-        float bv = (jok && kk < out_d) ? wlds[kk * wrow + j] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-      }
-    } else if (wstage_mode == 2) {
-      for (int k0 = 0; k0 < out_d; k0 += 4) {
-        const int kk = k0 + k;
-        float a = (kk < out_d) ? dz[(wr0 + i) * LDSW + kk] : 0.f;
-        float bv = (jok && kk < out_d) ? W[(long)kk * in_d + j] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-      }
-    } else {
-      // per-wave staged chunks of W[c0..c0+KCHUNK)[jt..jt+16)
-      for (int c0 = 0; c0 < out_d; c0 += KCHUNK) {
-        const int clen = min(KCHUNK, out_d - c0);
-        for (int idx = lane; idx < clen * 16; idx += 64) {
-          int r = idx / 16, c = idx % 16;
-          float v = (jt + c < in_d) ? W[(long)(c0 + r) * in_d + jt + c] : 0.f;
-          wv[r * 18 + c] = v;
-        }
-        wave_lds_fence();
-        for (int k0 = 0; k0 < clen; k0 += 4) {
-          const int kk = k0 + k;
-          float a = (kk < clen) ? dz[(wr0 + i) * LDSW + c0 + kk] : 0.f;
-          float bv = (kk < clen) ? wv[kk * 18 + i] : 0.f;
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
-        }
-        wave_lds_fence();
-      }
+    for (int k0 = 0; k0 < out_d; k0 += 4) {
+      const int kk = k0 + k;
+      float a = (kk < out_d) ? dz[(wr0 + i) * LDSW + kk] : 0.f;
+      float bv = (jok && kk < out_d) ? wlds[kk * wrow + j] : 0.f;
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
     }
     if (jok) {
       #pragma unroll
@@ -1411,9 +1337,10 @@ __global__ __launch_bounds__(256) void mlp_bwd_wide_both_f32(
   }
 }
 
-// host-side dispatch over the (ROWS, MAXW) instantiations — called from
-// bindings.hip so template symbols stay in this translation unit
-template <int ROWS, bool BF16, bool DO_FWD>
+// host-side dispatch over the instantiations — called from bindings.hip so
+// template symbols stay in this translation unit.  The whole-net backward
+// runs 32-row blocks only (BWD_FUSED_ROWS, bindings.hip).
+template <bool BF16, bool DO_FWD>
 static void launch_mlp_bwd_fused_t(bool need_dx, const MLPBwdArgs& args,
                                    const float* x, const float* dy, float* dx,
                                    float* ws, const float* mse_returns,
@@ -1421,11 +1348,11 @@ static void launch_mlp_bwd_fused_t(bool need_dx, const MLPBwdArgs& args,
                                    int n_blocks, hipStream_t stream,
                                    const GaussSeedArgs& gargs) {
   if (need_dx)
-    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<ROWS, BF16, DO_FWD, true>),
+    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, BF16, DO_FWD, true>),
                        dim3(n_blocks), dim3(256), lds_bytes, stream, args, x,
                        dy, dx, ws, mse_returns, loss_partials, gargs);
   else
-    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<ROWS, BF16, DO_FWD, false>),
+    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, BF16, DO_FWD, false>),
                        dim3(n_blocks), dim3(256), lds_bytes, stream, args, x,
                        dy, dx, ws, mse_returns, loss_partials, gargs);
 }
@@ -1436,34 +1363,24 @@ void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
                           const float* dy, float* dx, float* ws,
                           const float* mse_returns, float* loss_partials,
                           size_t lds_bytes, int n_blocks, int compute_bf16,
-                          hipStream_t stream, int rows, int do_fwd,
-                          GaussSeedArgs gargs, int need_dx) {
+                          hipStream_t stream, int do_fwd, GaussSeedArgs gargs,
+                          int need_dx) {
   const bool ndx = need_dx != 0;
 #define BWD_FUSED_ARGS \
   ndx, args, x, dy, dx, ws, mse_returns, loss_partials, lds_bytes, n_blocks, \
       stream, gargs
-  if (do_fwd) {  // fp32 only (host gates)
-    if (rows == 16) launch_mlp_bwd_fused_t<16, false, true>(BWD_FUSED_ARGS);
-    else launch_mlp_bwd_fused_t<32, false, true>(BWD_FUSED_ARGS);
-  } else if (rows == 16) {
-    if (compute_bf16) launch_mlp_bwd_fused_t<16, true, false>(BWD_FUSED_ARGS);
-    else launch_mlp_bwd_fused_t<16, false, false>(BWD_FUSED_ARGS);
-  } else {
-    if (compute_bf16) launch_mlp_bwd_fused_t<32, true, false>(BWD_FUSED_ARGS);
-    else launch_mlp_bwd_fused_t<32, false, false>(BWD_FUSED_ARGS);
-  }
+  // the in-kernel forward is fp32 only (host gates)
+  if (do_fwd) launch_mlp_bwd_fused_t<false, true>(BWD_FUSED_ARGS);
+  else if (compute_bf16) launch_mlp_bwd_fused_t<true, false>(BWD_FUSED_ARGS);
+  else launch_mlp_bwd_fused_t<false, false>(BWD_FUSED_ARGS);
 #undef BWD_FUSED_ARGS
 }
 
 // lds_bytes: the larger of the two halves' budgets; grid (n_blocks, 2)
 void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
-                               int n_blocks, int rows, hipStream_t stream) {
-  if (rows == 16)
-    hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<16>), dim3(n_blocks, 2),
-                       dim3(256), lds_bytes, stream, a);
-  else
-    hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32>), dim3(n_blocks, 2),
-                       dim3(256), lds_bytes, stream, a);
+                               int n_blocks, hipStream_t stream) {
+  hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32>), dim3(n_blocks, 2),
+                     dim3(256), lds_bytes, stream, a);
 }
 
 // Both nets must be [in <= 64, 64, 32, out <= 16] fp32 on 32-row blocks
@@ -1512,41 +1429,38 @@ void launch_mlp_dgrad_wide(const float* dy, const float* y, const float* W,
                      act);
 }
 
+// narrow nets only (widths <= 64); rows in {16, 32, 64}
 void launch_mlp_fwd(const MLPArgs& args, const float* x, int save_hidden,
-                    int rows, int maxw, int n_blocks, int wstage_mode,
-                    size_t lds_bytes, int compute_bf16, hipStream_t stream) {
+                    int rows, int n_blocks, size_t lds_bytes, int compute_bf16,
+                    hipStream_t stream) {
   dim3 g(n_blocks), b(256);
-  if (compute_bf16 && maxw == 64 && wstage_mode == 0) {
-    if (rows == 16)
-      hipLaunchKernelGGL((fused_mlp_fwd_f32_t<16, 64, true>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-    else if (rows == 32)
-      hipLaunchKernelGGL((fused_mlp_fwd_f32_t<32, 64, true>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-    else
-      hipLaunchKernelGGL((fused_mlp_fwd_f32_t<64, 64, true>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-    return;
+#define FWD_LAUNCH(ROWS, BF16)                                               \
+  hipLaunchKernelGGL((fused_mlp_fwd_f32_t<ROWS, 64, BF16>), g, b, lds_bytes, \
+                     stream, args, x, save_hidden)
+  if (compute_bf16) {
+    if (rows == 16) FWD_LAUNCH(16, true);
+    else if (rows == 32) FWD_LAUNCH(32, true);
+    else FWD_LAUNCH(64, true);
+  } else {
+    if (rows == 16) FWD_LAUNCH(16, false);
+    else if (rows == 32) FWD_LAUNCH(32, false);
+    else FWD_LAUNCH(64, false);
   }
-  if (rows == 16 && maxw == 64)
-    hipLaunchKernelGGL((fused_mlp_fwd_f32_t<16, 64>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-  else if (rows == 32 && maxw == 64)
-    hipLaunchKernelGGL((fused_mlp_fwd_f32_t<32, 64>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-  else if (rows == 64 && maxw == 64)
-    hipLaunchKernelGGL((fused_mlp_fwd_f32_t<64, 64>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
-  else
-    hipLaunchKernelGGL((fused_mlp_fwd_f32_t<32, 256>), g, b, lds_bytes, stream, args, x, save_hidden, wstage_mode);
+#undef FWD_LAUNCH
 }
 
+// narrow nets only (widths <= 64); rows in {32, 64}
 void launch_mlp_bwd_layer(const float* dy, const float* y, const float* xin,
                           const float* W, float* dx, float* ws, long ws_stride,
                           int batch, int out_d, int in_d, int act, int rows,
-                          int maxw, int n_blocks, int wstage_mode,
-                          size_t lds_bytes, hipStream_t stream) {
+                          int n_blocks, size_t lds_bytes, hipStream_t stream) {
   dim3 g(n_blocks), b(256);
-  if (rows == 32 && maxw == 64)
-    hipLaunchKernelGGL((mlp_bwd_layer_f32_t<32, 64>), g, b, lds_bytes, stream, dy, y, xin, W, dx, ws, ws_stride, batch, out_d, in_d, act, wstage_mode);
-  else if (rows == 64 && maxw == 64)
-    hipLaunchKernelGGL((mlp_bwd_layer_f32_t<64, 64>), g, b, lds_bytes, stream, dy, y, xin, W, dx, ws, ws_stride, batch, out_d, in_d, act, wstage_mode);
+  if (rows == 32)
+    hipLaunchKernelGGL((mlp_bwd_layer_f32_t<32, 64>), g, b, lds_bytes, stream,
+                       dy, y, xin, W, dx, ws, ws_stride, batch, out_d, in_d, act);
   else
-    hipLaunchKernelGGL((mlp_bwd_layer_f32_t<32, 256>), g, b, lds_bytes, stream, dy, y, xin, W, dx, ws, ws_stride, batch, out_d, in_d, act, wstage_mode);
+    hipLaunchKernelGGL((mlp_bwd_layer_f32_t<64, 64>), g, b, lds_bytes, stream,
+                       dy, y, xin, W, dx, ws, ws_stride, batch, out_d, in_d, act);
 }
 
 // ---------------------------------------------------------------------------

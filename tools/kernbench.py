@@ -3,7 +3,7 @@
 Run on a GPU box:  python tools/kernbench.py
 Prints per-kernel microseconds (median of repeats, event-timed) for the
 PPO HalfCheetah config (policy [17,64,32,6], value [17,64,32,1],
-B=4000) under both ROWS tilings, plus the loss/scan/update kernels.
+B=4000), plus the loss/scan/update kernels.
 """
 import os
 import sys
@@ -37,33 +37,34 @@ def main():
     B = 4000
     results = {}
 
-    for rows in (16, 32, 64):
-        os.environ["RL_REPLICAS_AMD_MLP_ROWS"] = str(rows)
-        mlp = MLP([17, 64, 32, 6]).to(dev)
-        from rl_replicas_amd.ops.fused_mlp import _extract_layers
+    # The forward row tile is the extension's default for this batch;
+    # RL_REPLICAS_AMD_MLP_ROWS is read once per process, so a sweep over
+    # tiles is one run of this tool per value, not a loop in here.
+    rows = os.environ.get("RL_REPLICAS_AMD_MLP_ROWS", "default")
+    from rl_replicas_amd.ops.fused_mlp import _extract_layers
 
-        weights, biases, acts = _extract_layers(mlp)
-        x = torch.randn(B, 17, device=dev)
-        results[f"fwd_nosave_rows{rows}"] = time_fn(
-            lambda: ext.mlp_forward(x, list(weights), list(biases), acts, False)
-        )
-        results[f"fwd_save_rows{rows}"] = time_fn(
-            lambda: ext.mlp_forward(x, list(weights), list(biases), acts, True)
-        )
-        outs = ext.mlp_forward(x, list(weights), list(biases), acts, True)
-        dy = torch.randn_like(outs[0])
-        results[f"bwd_rows{rows}"] = time_fn(
-            lambda: ext.mlp_backward(dy, x, list(weights), list(biases),
-                                     list(outs[1:]), outs[0], acts)
-        )
-        # off-policy width
-        q = MLP([23, 256, 256, 1]).to(dev)
-        wq, bq, aq = _extract_layers(q)
-        xq = torch.randn(100, 23, device=dev)
-        results[f"qfwd100_rows{rows}"] = time_fn(
-            lambda: ext.mlp_forward(xq, list(wq), list(bq), aq, False)
-        )
-    os.environ.pop("RL_REPLICAS_AMD_MLP_ROWS")
+    mlp = MLP([17, 64, 32, 6]).to(dev)
+    weights, biases, acts = _extract_layers(mlp)
+    x = torch.randn(B, 17, device=dev)
+    results[f"fwd_nosave_rows_{rows}"] = time_fn(
+        lambda: ext.mlp_forward(x, list(weights), list(biases), acts, False)
+    )
+    results[f"fwd_save_rows_{rows}"] = time_fn(
+        lambda: ext.mlp_forward(x, list(weights), list(biases), acts, True)
+    )
+    outs = ext.mlp_forward(x, list(weights), list(biases), acts, True)
+    dy = torch.randn_like(outs[0])
+    results["bwd"] = time_fn(
+        lambda: ext.mlp_backward(dy, x, list(weights), list(biases),
+                                 list(outs[1:]), outs[0], acts)
+    )
+    # off-policy width
+    q = MLP([23, 256, 256, 1]).to(dev)
+    wq, bq, aq = _extract_layers(q)
+    xq = torch.randn(100, 23, device=dev)
+    results["qfwd100"] = time_fn(
+        lambda: ext.mlp_forward(xq, list(wq), list(bq), aq, False)
+    )
 
     # losses
     mean = torch.randn(B, 6, device=dev)
