@@ -8,8 +8,10 @@ update runs as:
       share two launches — a twin kernel that runs forward, loss seed and
       whole-net backward of both nets with LDS-resident activations, and a
       twin reduce+Adam with the KL early-stop gate folded in.  Narrow fp32
-      identity-head Gaussian policy, narrow value net, both on FusedAdam,
-      P <= V, no per-iteration collectives.
+      identity-head Gaussian or categorical policy, narrow value net, both
+      on FusedAdam, P <= V, no per-iteration collectives
+      (RL_REPLICAS_AMD_CATEGORICAL_ITER=0 keeps categorical policies on the
+      per-iteration pipeline below).
   separate graphs (_GraphedPPO, _GraphedValueLoop): the same two-kernel
       iterations per net where each is eligible (chunked capture for the
       policy's early stop); otherwise a captured per-iteration pipeline of
@@ -249,16 +251,45 @@ def _fwd_in_kernel_fits(weights) -> bool:
 
 
 def _mega_eligible(policy, kind: str, obs: Tensor) -> bool:
-    """The 2-kernel policy iteration (gaussian_ppo_policy_iter): narrow
-    fp32 identity-head Gaussian policies (the bench config)."""
-    if kind != "gaussian" or ops.compute_bf16() != 0:
+    """The 2-kernel policy iteration (gaussian_ppo_policy_iter /
+    categorical_ppo_policy_iter): narrow fp32 identity-head policies.
+    Gaussian (the bench config) reserves one argument-block slot for the
+    log_std pseudo-layer; categorical has none.
+    RL_REPLICAS_AMD_CATEGORICAL_ITER=0 keeps categorical policies on the
+    multi-kernel loop."""
+    if kind not in ("gaussian", "categorical") or ops.compute_bf16() != 0:
+        return False
+    if kind == "categorical" and not _categorical_iter_enabled():
         return False
     weights, _, acts = _extract_layers(_mlp_of(policy))
+    if kind == "categorical" and (
+        obs.dtype != torch.float32
+        or any(w.dtype != torch.float32 for w in weights)
+    ):
+        return False
+    reserve = 1 if kind == "gaussian" else 0
+    head = policy.log_std.numel() if kind == "gaussian" else int(weights[-1].shape[0])
     return (
         acts[-1] == 0  # identity head
-        and policy.log_std.numel() <= _limits()[2]
-        and _fused_bwd_fits(obs.shape[1], weights, reserve=1)[1]
+        and head <= _limits()[2]
+        and _fused_bwd_fits(obs.shape[1], weights, reserve=reserve)[1]
     )
+
+
+def _categorical_iter_enabled() -> bool:
+    return os.environ.get("RL_REPLICAS_AMD_CATEGORICAL_ITER", "1") != "0"
+
+
+def _policy_iter_binding(ext, policy, kind: str, twin: bool):
+    """(binding, seed args, tail args): the fused policy iteration of the
+    policy's kind — the Gaussian argument list carries log_std after the
+    advantages and its Adam state after the net's; categorical has neither."""
+    name = "%s_ppo_%s" % (kind, "value_twin_iter" if twin else "policy_iter")
+    if kind == "gaussian":
+        ls_state = policy.optimizer.state[policy.log_std]
+        return (getattr(ext, name), [policy.log_std.data],
+                [ls_state["exp_avg"], ls_state["exp_avg_sq"]])
+    return getattr(ext, name), [], []
 
 
 class _CapturedLoop:
@@ -368,10 +399,11 @@ class _GraphedPPO:
 
             # mega path: ONE 2-kernel launch sequence per iteration
             # (DO_FWD fused fwd+KL+loss+bwd, then merged reduce+Adam
-            # incl. the log_std slot with the gate bookkeeping folded
-            # in) — narrow fp32 identity-head Gaussian policies (the
-            # bench config)
+            # incl. the Gaussian log_std slot with the gate bookkeeping
+            # folded in) — narrow fp32 identity-head policies (the
+            # bench config; categorical: no log_std state)
             use_mega = _mega_eligible(policy, kind, obs0)
+            self.use_mega = use_mega
             if use_mega:
                 from rl_replicas_amd.ops.fused_adam import adam_arg_lists
 
@@ -379,9 +411,10 @@ class _GraphedPPO:
                 m2l, v2l, step0, hp = adam_arg_lists(
                     policy.optimizer, weights0, biases0
                 )
-                # created by _ensure_adam_state above
-                ls_state = policy.optimizer.state[policy.log_std]
-                ls_m, ls_v = ls_state["exp_avg"], ls_state["exp_avg_sq"]
+                # log_std state: created by _ensure_adam_state above
+                policy_iter, seed_args, ls_mv = _policy_iter_binding(
+                    ext, policy, kind, twin=False
+                )
                 scratch_loss = torch.zeros(1, device=dev)
 
             def make_chunk(start: int, count: int):
@@ -391,11 +424,11 @@ class _GraphedPPO:
                         self.iters_done.zero_()
                     if use_mega:
                         for i in range(start, start + count):
-                            ext.gaussian_ppo_policy_iter(
+                            policy_iter(
                                 self.obs, list(weights0), list(biases0), acts0,
                                 self.actions, self.old_logp, self.adv,
-                                policy.log_std.data, clip, m2l, v2l, ls_m,
-                                ls_v, step0, *hp, float(i), self.gate,
+                                *seed_args, clip, m2l, v2l, *ls_mv,
+                                step0, *hp, float(i), self.gate,
                                 self.kl_final, self.iters_done, thr,
                                 self.loss0 if i == 0 else scratch_loss,
                                 i == 0,
@@ -661,7 +694,8 @@ class _GraphedValueLoop:
 class _GraphedPPOTwin:
     """A whole PPO epoch's update — policy loop, value loop and their
     epilogues — as ONE graph, with policy iteration i and value iteration
-    i sharing two launches (gaussian_ppo_value_twin_iter).
+    i sharing two launches (gaussian_ppo_value_twin_iter, or
+    categorical_ppo_value_twin_iter for a categorical policy).
 
     The two loops are independent (advantages and returns are computed
     before either runs; neither net reads the other), so pairing them
@@ -699,8 +733,11 @@ class _GraphedPPOTwin:
         pm, pv, pstep, php = adam_arg_lists(policy.optimizer, pw, pb)
         state = [p.data for p in policy.parameters()]
         state += _ensure_adam_state(policy.optimizer)
-        ls_state = policy.optimizer.state[policy.log_std]
-        ls_m, ls_v = ls_state["exp_avg"], ls_state["exp_avg_sq"]
+        kind = _policy_kind(policy)
+        self.kind = kind
+        twin_iter, seed_args, ls_mv = _policy_iter_binding(
+            ext, policy, kind, twin=True
+        )
 
         vw, vb, vacts = _extract_layers(vmlp)
         vm, vv, vstep, vhp = adam_arg_lists(vf.optimizer, vw, vb)
@@ -714,10 +751,10 @@ class _GraphedPPOTwin:
             self.gate.fill_(1.0)
             self.iters_done.zero_()
             for i in range(num_p):
-                ext.gaussian_ppo_value_twin_iter(
+                twin_iter(
                     self.obs, list(pw), list(pb), pacts, self.actions,
-                    self.old_logp, self.adv, policy.log_std.data, clip, pm,
-                    pv, ls_m, ls_v, pstep, *php, float(i), self.gate,
+                    self.old_logp, self.adv, *seed_args, clip, pm,
+                    pv, *ls_mv, pstep, *php, float(i), self.gate,
                     self.kl_final, self.iters_done, thr,
                     self.loss0 if i == 0 else scratch_loss, i == 0,
                     self.obs, list(vw), list(vb), vacts, self.returns,
@@ -731,8 +768,12 @@ class _GraphedPPOTwin:
                 )
             # policy epilogue: the final executed iteration's KL is still
             # pending; after it iters_done IS the executed-update count
-            kl = ext.gaussian_kl(_forward_only(pmlp, self.obs), self.actions,
-                                 policy.log_std.data, self.old_logp)
+            out = _forward_only(pmlp, self.obs)
+            if kind == "gaussian":
+                kl = ext.gaussian_kl(out, self.actions, policy.log_std.data,
+                                     self.old_logp)
+            else:
+                kl = ext.categorical_kl(out, self.actions, self.old_logp)
             ext.ppo_gate_update_(self.gate, kl, self.kl_final,
                                  self.iters_done, thr)
             policy.optimizer.bump_steps_by(self.iters_done)
@@ -797,7 +838,9 @@ def ppo_twin_eligible(algo, obs: Tensor) -> bool:
     and the fp32 narrow in-kernel-forward value iteration are both
     eligible, both optimizers are FusedAdam, graphs are on, the loops
     capture whole (no per-iteration collectives) and P <= V.
-    RL_REPLICAS_AMD_PPO_TWIN=0 selects the separate loops.
+    RL_REPLICAS_AMD_PPO_TWIN=0 selects the separate loops (the fused
+    policy iteration still runs there); RL_REPLICAS_AMD_CATEGORICAL_ITER=0
+    takes categorical policies off the fused iteration altogether.
     RL_REPLICAS_AMD_TWIN_SHAPED=0 keeps the twin launch on the generic
     kernel where the [in, 64, 32, out] shaped one would run (the
     extension reads it per call; a captured graph keeps its kernel)."""
@@ -819,7 +862,9 @@ def ppo_twin_eligible(algo, obs: Tensor) -> bool:
     ext = ops._load_extension()
     fb = int(ext.value_loss_partials_blocks(obs.shape[0]))
     pweights = _extract_layers(_mlp_of(policy))[0]
-    grand_p = sum(w.numel() + w.shape[0] for w in pweights) + policy.log_std.numel()
+    grand_p = sum(w.numel() + w.shape[0] for w in pweights)
+    if _policy_kind(policy) == "gaussian":
+        grand_p += policy.log_std.numel()  # the pseudo-layer
     grand_v = sum(w.numel() + w.shape[0] for w in vweights)
     return bool(ext.reduce_adam_is_staged(fb, grand_p)
                 and ext.reduce_adam_is_staged(fb, grand_v))

@@ -1271,9 +1271,9 @@ void ppo_gate_update_(torch::Tensor gate, torch::Tensor kl,
   HIP_OK(hipGetLastError());
 }
 
-// ONE captured Gaussian-PPO policy iteration = 2 kernels:
+// ONE captured PPO policy iteration = 2 kernels:
 //   1. DO_FWD fused kernel: forward (LDS activations) + pending-KL /
-//      loss / dlog_std partials + clipped-surrogate dZ seed + whole-net
+//      loss (/ dlog_std) partials + clipped-surrogate dZ seed + whole-net
 //      backward stage-1 (no input gradient).  After the first iteration
 //      it returns at once while the gate is closed: a frozen iteration
 //      costs a launch, not a kernel.
@@ -1283,12 +1283,27 @@ void ppo_gate_update_(torch::Tensor gate, torch::Tensor kl,
 //      1.5*maxkl (so this iteration's update is skipped, like the
 //      reference's break at ppo.py:176-181); workgroup 0 records gate,
 //      kl_final, iters_done and the iteration-0 loss.
-// Narrow fp32 identity-head Gaussian policies only (the bench config).
-// The returned tensor is the (empty) dx slot.
+// Narrow fp32 identity-head policies only: Gaussian (the bench config) or
+// categorical, which has no log_std and so no pseudo-layer — its seed is
+// the row softmax over the head tile.  The returned tensor is the (empty)
+// dx slot.
 namespace {
 
-// everything one Gaussian-PPO policy iteration launches with: the fused
-// kernel's argument blocks, the reduce+Adam block (log_std pseudo-layer
+// what tells the two policy kinds apart on the host: the seed kind and,
+// for Gaussian, log_std with its Adam state (the pseudo-layer)
+struct PolicySeed {
+  int kind;  // SEED_GAUSSIAN | SEED_CATEGORICAL
+  const torch::Tensor* log_std = nullptr;
+  const torch::Tensor* ls_m = nullptr;
+  const torch::Tensor* ls_v = nullptr;
+  bool gaussian() const { return kind == SEED_GAUSSIAN; }
+  // argument-block slots / workspace elements of the pseudo-layer
+  int reserve() const { return gaussian() ? 1 : 0; }
+  int64_t extra(int D) const { return gaussian() ? D : 0; }
+};
+
+// everything one PPO policy iteration launches with: the fused kernel's
+// argument blocks, the reduce+Adam block (log_std pseudo-layer if any
 // and gate bookkeeping included) and the buffers they point into
 struct PolicyIterBlocks {
   MLPBwdArgs ba;
@@ -1300,20 +1315,20 @@ struct PolicyIterBlocks {
   int64_t grand_ls;
 };
 
-// every check of one Gaussian-PPO policy iteration's arguments
+// every check of one PPO policy iteration's arguments
 NetLayout check_policy_iter(
-    const torch::Tensor& x, const std::vector<torch::Tensor>& weights,
+    const PolicySeed& seed, const torch::Tensor& x,
+    const std::vector<torch::Tensor>& weights,
     const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
     const torch::Tensor& actions, const torch::Tensor& old_logp,
-    const torch::Tensor& advantages, const torch::Tensor& log_std,
-    const std::vector<torch::Tensor>& adam_m,
-    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& ls_m,
-    const torch::Tensor& ls_v, const torch::Tensor& adam_step,
+    const torch::Tensor& advantages, const std::vector<torch::Tensor>& adam_m,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& adam_step,
     const torch::Tensor& gate, const torch::Tensor& kl_final,
     const torch::Tensor& iters_done, const torch::Tensor& loss_out) {
-  // one slot of the fixed argument arrays goes to the log_std pseudo-layer
+  // Gaussian: one slot of the fixed argument arrays goes to the log_std
+  // pseudo-layer
   const NetLayout net =
-      net_layout(x, weights, biases, acts, MLP_NARROW_WIDTH, 1);
+      net_layout(x, weights, biases, acts, MLP_NARROW_WIDTH, seed.reserve());
   const int64_t batch = x.size(0);
   const int D = net.dims[net.L];
   TORCH_CHECK(acts[net.L - 1] == 0, "needs an identity head");
@@ -1321,12 +1336,16 @@ NetLayout check_policy_iter(
   check_f32_gpu(actions, "actions");
   check_f32_gpu(old_logp, "old_logp");
   check_f32_gpu(advantages, "advantages");
-  TORCH_CHECK(actions.numel() == batch * D && old_logp.numel() == batch &&
-                  advantages.numel() == batch,
-              "actions/old_logp/advantages must be [batch, D]/[batch]/[batch]");
-  for (const torch::Tensor* t : {&log_std, &ls_m, &ls_v}) {
-    check_f32_gpu(*t, "log_std and its adam state");
-    TORCH_CHECK(t->numel() == D, "log_std and its adam state must be [D]");
+  // Gaussian actions are [batch, D]; categorical ones a class index per row
+  TORCH_CHECK(actions.numel() == (seed.gaussian() ? batch * D : batch) &&
+                  old_logp.numel() == batch && advantages.numel() == batch,
+              "actions/old_logp/advantages must be [batch, D] (Gaussian) or "
+              "[batch] (categorical) / [batch] / [batch]");
+  if (seed.gaussian()) {
+    for (const torch::Tensor* t : {seed.log_std, seed.ls_m, seed.ls_v}) {
+      check_f32_gpu(*t, "log_std and its adam state");
+      TORCH_CHECK(t->numel() == D, "log_std and its adam state must be [D]");
+    }
   }
   check_adam_state(weights, biases, adam_m, adam_v, adam_step);
   for (const torch::Tensor* t : {&gate, &kl_final, &iters_done, &loss_out}) {
@@ -1337,14 +1356,14 @@ NetLayout check_policy_iter(
 }
 
 PolicyIterBlocks build_policy_iter(
-    const NetLayout& net, const torch::Tensor& x,
+    const PolicySeed& seed, const NetLayout& net, const torch::Tensor& x,
     const std::vector<torch::Tensor>& weights,
     const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
     const torch::Tensor& actions, const torch::Tensor& old_logp,
-    const torch::Tensor& advantages, const torch::Tensor& log_std, double clip,
+    const torch::Tensor& advantages, double clip,
     const std::vector<torch::Tensor>& adam_m,
-    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& ls_m,
-    const torch::Tensor& ls_v, const torch::Tensor& adam_step, double lr,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& adam_step,
+    double lr,
     double beta1, double beta2, double eps, double weight_decay,
     double step_delta, const torch::Tensor& gate, const torch::Tensor& kl_final,
     const torch::Tensor& iters_done, double thr, const torch::Tensor& loss_out,
@@ -1355,7 +1374,7 @@ PolicyIterBlocks build_policy_iter(
   auto opts = x.options();
 
   PolicyIterBlocks pb;
-  pb.grand_ls = net.grand + D;  // + dlog_std pseudo-layer
+  pb.grand_ls = net.grand + seed.extra(D);  // + dlog_std pseudo-layer
   pb.fused_lds = fused_bwd_lds(net, true);
   pb.fb = (batch + BWD_FUSED_ROWS - 1) / BWD_FUSED_ROWS;
 
@@ -1369,7 +1388,8 @@ PolicyIterBlocks build_policy_iter(
   ga.actions = actions.data_ptr<float>();
   ga.old_logp = old_logp.data_ptr<float>();
   ga.adv = advantages.data_ptr<float>();
-  ga.log_std = log_std.data_ptr<float>();
+  ga.kind = seed.kind;
+  ga.log_std = seed.gaussian() ? seed.log_std->data_ptr<float>() : nullptr;
   ga.kl_partials = pb.kl_partials.data_ptr<float>();
   ga.dls_off = (int)net.grand;
   ga.clip = (float)clip;
@@ -1381,16 +1401,18 @@ PolicyIterBlocks build_policy_iter(
   ra = fill_reduce_adam(weights, biases, net, pb.ws.data_ptr<float>(),
                         pb.grand_ls, pb.fb, adam_m, adam_v, adam_step, lr,
                         beta1, beta2, eps, weight_decay, step_delta, gate);
-  ra.n_layers = L + 1;
-  // log_std pseudo-layer: bias-only (wsize 0)
-  ra.pw[L] = nullptr;
-  ra.pb[L] = log_std.data_ptr<float>();
-  ra.mw[L] = nullptr;
-  ra.mb[L] = ls_m.data_ptr<float>();
-  ra.vw[L] = nullptr;
-  ra.vb[L] = ls_v.data_ptr<float>();
-  ra.total[L] = D;
-  ra.wsize[L] = 0;
+  if (seed.gaussian()) {
+    ra.n_layers = L + 1;
+    // log_std pseudo-layer: bias-only (wsize 0)
+    ra.pw[L] = nullptr;
+    ra.pb[L] = seed.log_std->data_ptr<float>();
+    ra.mw[L] = nullptr;
+    ra.mb[L] = seed.ls_m->data_ptr<float>();
+    ra.vw[L] = nullptr;
+    ra.vb[L] = seed.ls_v->data_ptr<float>();
+    ra.total[L] = D;
+    ra.wsize[L] = 0;
+  }
   // gate bookkeeping block: every workgroup derives the open/closed
   // decision itself from the partials, workgroup 0 records it
   ra.kl_partials = pb.kl_partials.data_ptr<float>();
@@ -1405,6 +1427,38 @@ PolicyIterBlocks build_policy_iter(
   return pb;
 }
 
+// the policy iteration of either kind
+torch::Tensor ppo_policy_iter(
+    const PolicySeed& seed, const torch::Tensor& x,
+    const std::vector<torch::Tensor>& weights,
+    const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
+    const torch::Tensor& actions, const torch::Tensor& old_logp,
+    const torch::Tensor& advantages, double clip,
+    const std::vector<torch::Tensor>& adam_m,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& adam_step,
+    double lr, double beta1, double beta2, double eps, double weight_decay,
+    double step_delta, const torch::Tensor& gate, const torch::Tensor& kl_final,
+    const torch::Tensor& iters_done, double thr, const torch::Tensor& loss_out,
+    bool first_iter) {
+  const NetLayout net = check_policy_iter(
+      seed, x, weights, biases, acts, actions, old_logp, advantages, adam_m,
+      adam_v, adam_step, gate, kl_final, iters_done, loss_out);
+  const PolicyIterBlocks pb = build_policy_iter(
+      seed, net, x, weights, biases, acts, actions, old_logp, advantages, clip,
+      adam_m, adam_v, adam_step, lr, beta1, beta2, eps, weight_decay,
+      step_delta, gate, kl_final, iters_done, thr, loss_out, first_iter);
+  auto stream = current_stream();
+  // no input gradient: the update is fused, nobody reads dx
+  launch_mlp_bwd_fused(pb.ba, x.data_ptr<float>(), nullptr, nullptr,
+                       pb.ws.data_ptr<float>(), nullptr,
+                       pb.loss_partials.data_ptr<float>(), pb.fused_lds, pb.fb,
+                       0, stream, 1, pb.ga, 0);
+  HIP_OK(hipGetLastError());
+  launch_mlp_grad_reduce_adam(pb.ra, (long)pb.grand_ls, stream);
+  HIP_OK(hipGetLastError());
+  return torch::empty({0}, x.options());  // dx slot: never computed here
+}
+
 }  // namespace
 
 torch::Tensor gaussian_ppo_policy_iter(
@@ -1417,24 +1471,31 @@ torch::Tensor gaussian_ppo_policy_iter(
     double weight_decay, double step_delta, torch::Tensor gate,
     torch::Tensor kl_final, torch::Tensor iters_done, double thr,
     torch::Tensor loss_out, bool first_iter) {
-  const NetLayout net = check_policy_iter(
-      x, weights, biases, acts, actions, old_logp, advantages, log_std, adam_m,
-      adam_v, ls_m, ls_v, adam_step, gate, kl_final, iters_done, loss_out);
-  const PolicyIterBlocks pb = build_policy_iter(
-      net, x, weights, biases, acts, actions, old_logp, advantages, log_std,
-      clip, adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
-      weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
+  return ppo_policy_iter(
+      PolicySeed{SEED_GAUSSIAN, &log_std, &ls_m, &ls_v}, x, weights, biases,
+      acts, actions, old_logp, advantages, clip, adam_m, adam_v, adam_step, lr,
+      beta1, beta2, eps, weight_decay, step_delta, gate, kl_final, iters_done,
+      thr, loss_out, first_iter);
+}
+
+// gaussian_ppo_policy_iter for a categorical policy: no log_std, ls_m, ls_v;
+// actions is float32 [batch] (class indices, as categorical_policy_loss
+// takes them)
+torch::Tensor categorical_ppo_policy_iter(
+    torch::Tensor x, std::vector<torch::Tensor> weights,
+    std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
+    torch::Tensor actions, torch::Tensor old_logp, torch::Tensor advantages,
+    double clip, std::vector<torch::Tensor> adam_m,
+    std::vector<torch::Tensor> adam_v, torch::Tensor adam_step, double lr,
+    double beta1, double beta2, double eps, double weight_decay,
+    double step_delta, torch::Tensor gate, torch::Tensor kl_final,
+    torch::Tensor iters_done, double thr, torch::Tensor loss_out,
+    bool first_iter) {
+  return ppo_policy_iter(
+      PolicySeed{SEED_CATEGORICAL}, x, weights, biases, acts, actions,
+      old_logp, advantages, clip, adam_m, adam_v, adam_step, lr, beta1, beta2,
+      eps, weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
       first_iter);
-  auto stream = current_stream();
-  // no input gradient: the update is fused, nobody reads dx
-  launch_mlp_bwd_fused(pb.ba, x.data_ptr<float>(), nullptr, nullptr,
-                       pb.ws.data_ptr<float>(), nullptr,
-                       pb.loss_partials.data_ptr<float>(), pb.fused_lds, pb.fb,
-                       0, stream, 1, pb.ga, 0);
-  HIP_OK(hipGetLastError());
-  launch_mlp_grad_reduce_adam(pb.ra, (long)pb.grand_ls, stream);
-  HIP_OK(hipGetLastError());
-  return torch::empty({0}, x.options());  // dx slot: never computed here
 }
 
 // The shape-specialised twin kernel (mlp_bwd_fused_twin_shaped_f32) covers
@@ -1463,33 +1524,41 @@ static std::vector<int64_t> net_dims(const NetLayout& n) {
 // Policy iteration i and value iteration i of one PPO epoch in the SAME
 // two launches (the two loops are independent: neither reads what the
 // other writes):
-//   1. twin fused kernel, grid (fb, 2): the Gaussian-PPO half of
-//      gaussian_ppo_policy_iter and the fwd_in_kernel fused-Adam half of
-//      value_mlp_backward;
+//   1. twin fused kernel, grid (fb, 2): the policy half of
+//      gaussian_ppo_policy_iter / categorical_ppo_policy_iter and the
+//      fwd_in_kernel fused-Adam half of value_mlp_backward;
 //   2. twin reduce+Adam: the policy's gated update with its bookkeeping
 //      and the value net's ungated one.
-// Arguments are those of gaussian_ppo_policy_iter, then the value net's
+// Arguments are those of the policy iteration binding, then the value net's
 // (v_*).  v_partials_out is the caller's deferred loss-partials row.  Each
-// net's result is bitwise what its own binding gives.
-void gaussian_ppo_value_twin_iter(
-    torch::Tensor x, std::vector<torch::Tensor> weights,
-    std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
-    torch::Tensor actions, torch::Tensor old_logp, torch::Tensor advantages,
-    torch::Tensor log_std, double clip, std::vector<torch::Tensor> adam_m,
-    std::vector<torch::Tensor> adam_v, torch::Tensor ls_m, torch::Tensor ls_v,
-    torch::Tensor adam_step, double lr, double beta1, double beta2, double eps,
-    double weight_decay, double step_delta, torch::Tensor gate,
-    torch::Tensor kl_final, torch::Tensor iters_done, double thr,
-    torch::Tensor loss_out, bool first_iter, torch::Tensor v_x,
-    std::vector<torch::Tensor> v_weights, std::vector<torch::Tensor> v_biases,
-    std::vector<int64_t> v_acts, torch::Tensor returns,
-    torch::Tensor v_partials_out, std::vector<torch::Tensor> v_adam_m,
-    std::vector<torch::Tensor> v_adam_v, torch::Tensor v_adam_step,
-    double v_lr, double v_beta1, double v_beta2, double v_eps,
-    double v_weight_decay, double v_step_delta) {
+// net's result is bitwise what its own binding gives.  The shape-specialised
+// kernel has the Gaussian seed only: categorical nets always take the
+// generic twin kernel.
+namespace {
+
+void ppo_value_twin_iter(
+    const PolicySeed& seed, const torch::Tensor& x,
+    const std::vector<torch::Tensor>& weights,
+    const std::vector<torch::Tensor>& biases, const std::vector<int64_t>& acts,
+    const torch::Tensor& actions, const torch::Tensor& old_logp,
+    const torch::Tensor& advantages, double clip,
+    const std::vector<torch::Tensor>& adam_m,
+    const std::vector<torch::Tensor>& adam_v, const torch::Tensor& adam_step,
+    double lr, double beta1, double beta2, double eps, double weight_decay,
+    double step_delta, const torch::Tensor& gate, const torch::Tensor& kl_final,
+    const torch::Tensor& iters_done, double thr, const torch::Tensor& loss_out,
+    bool first_iter, const torch::Tensor& v_x,
+    const std::vector<torch::Tensor>& v_weights,
+    const std::vector<torch::Tensor>& v_biases,
+    const std::vector<int64_t>& v_acts, const torch::Tensor& returns,
+    const torch::Tensor& v_partials_out,
+    const std::vector<torch::Tensor>& v_adam_m,
+    const std::vector<torch::Tensor>& v_adam_v,
+    const torch::Tensor& v_adam_step, double v_lr, double v_beta1,
+    double v_beta2, double v_eps, double v_weight_decay, double v_step_delta) {
   const NetLayout net = check_policy_iter(
-      x, weights, biases, acts, actions, old_logp, advantages, log_std, adam_m,
-      adam_v, ls_m, ls_v, adam_step, gate, kl_final, iters_done, loss_out);
+      seed, x, weights, biases, acts, actions, old_logp, advantages, adam_m,
+      adam_v, adam_step, gate, kl_final, iters_done, loss_out);
   TORCH_CHECK(v_x.data_ptr() == x.data_ptr() && v_x.sizes() == x.sizes(),
               "the twin iteration needs the same x for both nets");
   const NetLayout vnet =
@@ -1504,19 +1573,20 @@ void gaussian_ppo_value_twin_iter(
   check_adam_state(v_weights, v_biases, v_adam_m, v_adam_v, v_adam_step);
   check_f32_gpu(v_partials_out, "v_partials_out");
   TORCH_CHECK(v_partials_out.numel() >= fb, "v_partials_out too small");
-  TORCH_CHECK(mlp_reduce_adam_is_staged(fb, (long)(net.grand + net.dims[net.L])) &&
+  TORCH_CHECK(mlp_reduce_adam_is_staged(
+                  fb, (long)(net.grand + seed.extra(net.dims[net.L]))) &&
                   mlp_reduce_adam_is_staged(fb, (long)vnet.grand),
               "the twin reduce needs both nets on the staged reduce");
   const bool shaped =
+      seed.gaussian() &&
       ppo_twin_uses_shaped(net_dims(net), net_dims(vnet), x.size(0));
   TORCH_CHECK(!shaped || mlp_bwd_fused_shaped_lds(net.dims[0]) <= 80 * 1024,
               "shaped twin kernel over its LDS budget");
 
   const PolicyIterBlocks pb = build_policy_iter(
-      net, x, weights, biases, acts, actions, old_logp, advantages, log_std,
-      clip, adam_m, adam_v, ls_m, ls_v, adam_step, lr, beta1, beta2, eps,
-      weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
-      first_iter);
+      seed, net, x, weights, biases, acts, actions, old_logp, advantages, clip,
+      adam_m, adam_v, adam_step, lr, beta1, beta2, eps, weight_decay,
+      step_delta, gate, kl_final, iters_done, thr, loss_out, first_iter);
   torch::Tensor v_ws = torch::empty({(int64_t)pb.fb, vnet.grand}, x.options());
 
   MLPBwdTwinArgs ta{};
@@ -1545,6 +1615,57 @@ void gaussian_ppo_value_twin_iter(
   launch_mlp_grad_reduce_adam_twin(pb.ra, (long)pb.grand_ls, vra,
                                    (long)vnet.grand, stream);
   HIP_OK(hipGetLastError());
+}
+
+}  // namespace
+
+void gaussian_ppo_value_twin_iter(
+    torch::Tensor x, std::vector<torch::Tensor> weights,
+    std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
+    torch::Tensor actions, torch::Tensor old_logp, torch::Tensor advantages,
+    torch::Tensor log_std, double clip, std::vector<torch::Tensor> adam_m,
+    std::vector<torch::Tensor> adam_v, torch::Tensor ls_m, torch::Tensor ls_v,
+    torch::Tensor adam_step, double lr, double beta1, double beta2, double eps,
+    double weight_decay, double step_delta, torch::Tensor gate,
+    torch::Tensor kl_final, torch::Tensor iters_done, double thr,
+    torch::Tensor loss_out, bool first_iter, torch::Tensor v_x,
+    std::vector<torch::Tensor> v_weights, std::vector<torch::Tensor> v_biases,
+    std::vector<int64_t> v_acts, torch::Tensor returns,
+    torch::Tensor v_partials_out, std::vector<torch::Tensor> v_adam_m,
+    std::vector<torch::Tensor> v_adam_v, torch::Tensor v_adam_step,
+    double v_lr, double v_beta1, double v_beta2, double v_eps,
+    double v_weight_decay, double v_step_delta) {
+  ppo_value_twin_iter(
+      PolicySeed{SEED_GAUSSIAN, &log_std, &ls_m, &ls_v}, x, weights, biases,
+      acts, actions, old_logp, advantages, clip, adam_m, adam_v, adam_step, lr,
+      beta1, beta2, eps, weight_decay, step_delta, gate, kl_final, iters_done,
+      thr, loss_out, first_iter, v_x, v_weights, v_biases, v_acts, returns,
+      v_partials_out, v_adam_m, v_adam_v, v_adam_step, v_lr, v_beta1, v_beta2,
+      v_eps, v_weight_decay, v_step_delta);
+}
+
+void categorical_ppo_value_twin_iter(
+    torch::Tensor x, std::vector<torch::Tensor> weights,
+    std::vector<torch::Tensor> biases, std::vector<int64_t> acts,
+    torch::Tensor actions, torch::Tensor old_logp, torch::Tensor advantages,
+    double clip, std::vector<torch::Tensor> adam_m,
+    std::vector<torch::Tensor> adam_v, torch::Tensor adam_step, double lr,
+    double beta1, double beta2, double eps, double weight_decay,
+    double step_delta, torch::Tensor gate, torch::Tensor kl_final,
+    torch::Tensor iters_done, double thr, torch::Tensor loss_out,
+    bool first_iter, torch::Tensor v_x, std::vector<torch::Tensor> v_weights,
+    std::vector<torch::Tensor> v_biases, std::vector<int64_t> v_acts,
+    torch::Tensor returns, torch::Tensor v_partials_out,
+    std::vector<torch::Tensor> v_adam_m, std::vector<torch::Tensor> v_adam_v,
+    torch::Tensor v_adam_step, double v_lr, double v_beta1, double v_beta2,
+    double v_eps, double v_weight_decay, double v_step_delta) {
+  ppo_value_twin_iter(
+      PolicySeed{SEED_CATEGORICAL}, x, weights, biases, acts, actions,
+      old_logp, advantages, clip, adam_m, adam_v, adam_step, lr, beta1, beta2,
+      eps, weight_decay, step_delta, gate, kl_final, iters_done, thr, loss_out,
+      first_iter, v_x, v_weights, v_biases, v_acts, returns, v_partials_out,
+      v_adam_m, v_adam_v, v_adam_step, v_lr, v_beta1, v_beta2, v_eps,
+      v_weight_decay, v_step_delta);
 }
 
 void counter_add_(torch::Tensor ctr, int64_t delta) {
@@ -1792,6 +1913,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one 2-kernel Gaussian-PPO policy iteration (gfx950)");
   m.def("gaussian_ppo_value_twin_iter", &gaussian_ppo_value_twin_iter,
         "PPO policy + value iteration in one twin kernel pair (gfx950)");
+  m.def("categorical_ppo_policy_iter", &categorical_ppo_policy_iter,
+        "one 2-kernel categorical-PPO policy iteration (gfx950)");
+  m.def("categorical_ppo_value_twin_iter", &categorical_ppo_value_twin_iter,
+        "categorical-PPO policy + value iteration in one twin kernel pair "
+        "(gfx950)");
   m.def("ppo_twin_uses_shaped", &ppo_twin_uses_shaped,
         "whether the twin iteration takes the [*,64,32,*] shaped kernel");
   m.def("reduce_adam_is_staged",

@@ -59,6 +59,17 @@ DEV_INLINE float dlogp_coeff(int mode, float logp, float old_logp, float adv,
   return -(g1 * s1 + (1.f - g1) * inclip * s1);
 }
 
+// log-sum-exp of one row of n logits (max-shifted).  The one definition:
+// the categorical loss kernels (loss_kernels.hip) and the categorical-PPO
+// seed of the fused iteration (mlp_kernels.hip) both take logp from it.
+DEV_INLINE float row_lse(const float* logits, int n) {
+  float m = logits[0];
+  for (int j = 1; j < n; ++j) m = fmaxf(m, logits[j]);
+  float s = 0.f;
+  for (int j = 0; j < n; ++j) s += __expf(logits[j] - m);
+  return m + __logf(s);
+}
+
 // wave-level f32 sum (64 lanes)
 DEV_INLINE float wave_reduce_sum(float v) {
   #pragma unroll
@@ -185,6 +196,13 @@ struct ReduceAdamArgs {
 // LDS-resident forward output, and the kernel additionally emits
 // per-block loss partials, pending-KL partials, and dlog_std partials
 // (written into the stage-1 workspace at dls_off as a pseudo-layer).
+// kind == SEED_CATEGORICAL: the head tile holds N = dims[L] logits per row,
+// `actions` is [B] (class index as fp32), the dZ seed is the clipped
+// surrogate's gradient through the row softmax, and there is no pseudo-
+// layer (log_std / dls_off unused).  The host picks the kernel
+// instantiation from `kind`; the Gaussian one never reads it.
+#define SEED_GAUSSIAN 0
+#define SEED_CATEGORICAL 1
 struct GaussSeedArgs {
   const float* actions;   // [B, D]; nullptr -> plain dy/mse seed
   const float* old_logp;  // [B]
@@ -193,14 +211,16 @@ struct GaussSeedArgs {
   float* kl_partials;     // [n_blocks]
   int dls_off;            // flat ws offset of the dlog_std pseudo-layer
   float clip;
+  int kind;               // SEED_GAUSSIAN | SEED_CATEGORICAL
   // optional: the whole kernel returns at once while *skip_gate == 0 (a
   // gate-frozen policy iteration; its partials are never read then)
   const float* skip_gate;
 };
 
-// twin PPO update launch (mlp_bwd_fused_twin_f32): the Gaussian-PPO policy
-// half and the value-MSE half of one update iteration, each with its own
-// net, workspace and partials; both read the same x.  ~0.5 KB by value.
+// twin PPO update launch (mlp_bwd_fused_twin_f32): the PPO policy half
+// (Gaussian or categorical seed, gauss.kind) and the value-MSE half of one
+// update iteration, each with its own net, workspace and partials; both
+// read the same x.  ~0.5 KB by value.
 struct MLPBwdTwinArgs {
   MLPBwdArgs pol;
   GaussSeedArgs gauss;

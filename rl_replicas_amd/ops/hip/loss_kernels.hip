@@ -285,16 +285,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void gaussian_kl_kernel(
 
 // ---------------------------------------------------------------------------
 // Categorical policy (categorical_policy.py:22-32): logp = logit_a - lse
-// outputs: dlogits[B,N], scalars[0]=loss
+// outputs: dlogits[B,N], scalars[0]=loss   (row_lse: common.h)
 // ---------------------------------------------------------------------------
-DEV_INLINE float row_lse(const float* logits, int n) {
-  float m = logits[0];
-  for (int j = 1; j < n; ++j) m = fmaxf(m, logits[j]);
-  float s = 0.f;
-  for (int j = 0; j < n; ++j) s += __expf(logits[j] - m);
-  return m + __logf(s);
-}
-
 __global__ __launch_bounds__(LOSS_P_THREADS) void categorical_policy_loss_bwd(
     const float* __restrict__ logits, const float* __restrict__ actions,
     const float* __restrict__ old_logp, const float* __restrict__ adv,

@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_layer_f32_t(
 // nets (mlp_bwd_fused_twin_f32 below).  `bx` is the workgroup's row block
 // and `WSN` the block count of the element-major workspace — blockIdx.x
 // and gridDim.x in the single-net kernel; `smem` is the dynamic LDS base.
-template <int ROWS, bool BF16, bool DO_FWD, bool NEED_DX>
+template <int ROWS, bool BF16, bool DO_FWD, bool NEED_DX, bool CAT = false>
 DEV_INLINE void mlp_bwd_fused_body(
     const MLPBwdArgs& args, const float* __restrict__ x,
     const float* __restrict__ dy, float* __restrict__ dx_out,
@@ -329,6 +329,65 @@ DEV_INLINE void mlp_bwd_fused_body(
       fin = hl;
     }
   }
+  // Categorical-PPO seed (CAT instantiations, DO_FWD fp32): per-row
+  // logp = logit[a] - lse from the LDS-resident head tile — what
+  // categorical_policy_loss_bwd and categorical_kl_kernel compute per row
+  // (loss_kernels.hip) — then loss + pending-KL partials and the softmax
+  // dZ seed.  No pseudo-layer.
+  if constexpr (CAT) {
+    static_assert(DO_FWD && !BF16 && ROWS <= 64, "categorical seed: fp32 DO_FWD");
+    const float* outl = hlds + (L - 1) * ROWS * LDSW;
+    const int N = args.dims[L];
+    __shared__ float cbuf[64];       // per-row dlogp coeff (ROWS <= 64)
+    __shared__ float lbuf[64];       // per-row loss
+    __shared__ float kbuf[64];       // per-row pending KL
+    __shared__ float sbuf[64];       // per-row log-sum-exp
+    __shared__ int abuf[64];         // per-row action index
+    const float inv_b = 1.f / (float)args.batch;
+    if (tid < ROWS) {
+      const int row = row0 + tid;
+      float lossr = 0.f, klr = 0.f, c = 0.f, lse = 0.f;
+      int a = 0;
+      if (row < args.batch) {
+        const float* lg = outl + tid * LDSW;
+        lse = row_lse(lg, N);
+        // clamped: a corrupt action never indexes outside the head tile
+        a = min(max((int)gargs.actions[row], 0), N - 1);
+        const float logp = lg[a] - lse;
+        klr = gargs.old_logp[row] - logp;
+        float lr_;
+        c = dlogp_coeff(1, logp, gargs.old_logp[row], gargs.adv[row],
+                        gargs.clip, &lr_) * inv_b;
+        lossr = lr_ * inv_b;
+      }
+      cbuf[tid] = c;
+      lbuf[tid] = lossr;
+      kbuf[tid] = klr;
+      sbuf[tid] = lse;
+      abuf[tid] = a;
+    }
+    __syncthreads();
+    // dZ seed = dlogits (identity head); tail rows have c == 0
+    for (int idx = tid; idx < ROWS * N; idx += 256) {
+      const int r = idx / N, j = idx % N;
+      float v = 0.f;
+      if (row0 + r < args.batch) {
+        const float p = __expf(outl[r * LDSW + j] - sbuf[r]);
+        v = cbuf[r] * (((j == abuf[r]) ? 1.f : 0.f) - p);
+      }
+      dza[r * LDSW + j] = v;
+    }
+    // fixed row order: deterministic
+    if (tid == 0) {
+      float sl = 0.f, sk = 0.f;
+      for (int r = 0; r < ROWS; ++r) {
+        sl += lbuf[r];
+        sk += kbuf[r];
+      }
+      loss_partials[bx] = sl;
+      gargs.kl_partials[bx] = sk;
+    }
+  } else
   // Gaussian-PPO seed (DO_FWD only): loss + pending-KL + dlog_std
   // partials and the dmean dZ seed, all from the LDS-resident forward
   if (DO_FWD && gargs.actions != nullptr) {
@@ -569,14 +628,15 @@ DEV_INLINE void mlp_bwd_fused_body(
   }
 }
 
-template <int ROWS, bool BF16 = false, bool DO_FWD = false, bool NEED_DX = true>
+template <int ROWS, bool BF16 = false, bool DO_FWD = false, bool NEED_DX = true,
+          bool CAT = false>
 __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
     MLPBwdArgs args, const float* __restrict__ x, const float* __restrict__ dy,
     float* __restrict__ dx_out, float* __restrict__ workspace,
     const float* __restrict__ mse_returns, float* __restrict__ loss_partials,
     GaussSeedArgs gargs = GaussSeedArgs{}) {
   extern __shared__ float smem[];
-  mlp_bwd_fused_body<ROWS, BF16, DO_FWD, NEED_DX>(
+  mlp_bwd_fused_body<ROWS, BF16, DO_FWD, NEED_DX, CAT>(
       args, x, dy, dx_out, workspace, mse_returns, loss_partials, gargs, smem,
       blockIdx.x, gridDim.x);
 }
@@ -584,15 +644,16 @@ __global__ __launch_bounds__(256) void mlp_bwd_fused_f32_t(
 // Twin launch of the PPO update: policy iteration i and value iteration i
 // are independent, have the same batch and the same row tiling, and each
 // alone fills half the chip, so one grid (fb, 2) runs both — blockIdx.y
-// 0 is the Gaussian-PPO half, 1 the value-MSE half.  Each half is the
+// 0 is the PPO policy half (Gaussian seed, or the categorical one in the
+// CAT instantiation), 1 the value-MSE half.  Each half is the
 // single-net body on its own argument block, workspace and partials; the
 // halves share nothing but x.  A gate-frozen policy half returns inside
 // the body before its first barrier (blockIdx.y is workgroup-uniform).
-template <int ROWS>
+template <int ROWS, bool CAT = false>
 __global__ __launch_bounds__(256) void mlp_bwd_fused_twin_f32(MLPBwdTwinArgs a) {
   extern __shared__ float smem[];
   if (blockIdx.y == 0) {
-    mlp_bwd_fused_body<ROWS, false, true, false>(
+    mlp_bwd_fused_body<ROWS, false, true, false, CAT>(
         a.pol, a.x, nullptr, nullptr, a.pol_ws, nullptr, a.pol_loss_partials,
         a.gauss, smem, blockIdx.x, gridDim.x);
   } else {
@@ -1369,8 +1430,14 @@ void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
 #define BWD_FUSED_ARGS \
   ndx, args, x, dy, dx, ws, mse_returns, loss_partials, lds_bytes, n_blocks, \
       stream, gargs
-  // the in-kernel forward is fp32 only (host gates)
-  if (do_fwd) launch_mlp_bwd_fused_t<false, true>(BWD_FUSED_ARGS);
+  // the in-kernel forward is fp32 only (host gates); the categorical seed
+  // is an instantiation of its own, so the Gaussian / value code is
+  // untouched by it
+  if (do_fwd && gargs.kind == SEED_CATEGORICAL) {
+    hipLaunchKernelGGL((mlp_bwd_fused_f32_t<32, false, true, false, true>),
+                       dim3(n_blocks), dim3(256), lds_bytes, stream, args, x,
+                       dy, dx, ws, mse_returns, loss_partials, gargs);
+  } else if (do_fwd) launch_mlp_bwd_fused_t<false, true>(BWD_FUSED_ARGS);
   else if (compute_bf16) launch_mlp_bwd_fused_t<true, false>(BWD_FUSED_ARGS);
   else launch_mlp_bwd_fused_t<false, false>(BWD_FUSED_ARGS);
 #undef BWD_FUSED_ARGS
@@ -1379,8 +1446,12 @@ void launch_mlp_bwd_fused(const MLPBwdArgs& args, const float* x,
 // lds_bytes: the larger of the two halves' budgets; grid (n_blocks, 2)
 void launch_mlp_bwd_fused_twin(const MLPBwdTwinArgs& a, size_t lds_bytes,
                                int n_blocks, hipStream_t stream) {
-  hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32>), dim3(n_blocks, 2),
-                     dim3(256), lds_bytes, stream, a);
+  if (a.gauss.kind == SEED_CATEGORICAL)
+    hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32, true>), dim3(n_blocks, 2),
+                       dim3(256), lds_bytes, stream, a);
+  else
+    hipLaunchKernelGGL((mlp_bwd_fused_twin_f32<32>), dim3(n_blocks, 2),
+                       dim3(256), lds_bytes, stream, a);
 }
 
 // Both nets must be [in <= 64, 64, 32, out <= 16] fp32 on 32-row blocks
