@@ -147,32 +147,71 @@ class DeviceVectorEnv:
 
 
 class DevicePendulumEnv:
-    """Pendulum-v1 as a lockstep device vector env (pure torch ops — the
-    identical code runs on CPU and GPU; no HIP kernel needed at N x 2
-    state sizes).  Dynamics/reward formulas match `classic.PendulumEnv`
-    exactly (fp64 state, fp32 obs); only the init RNG stream differs
-    (torch generator vs numpy).  Pendulum never terminates early, so the
-    lockstep-truncation contract of `DeviceSampler` holds.
+    """Pendulum-v1 as a lockstep device vector env.  Dynamics/reward
+    formulas match `classic.PendulumEnv` exactly (fp64 state, fp32 obs).
+    Pendulum never terminates early, so the lockstep-truncation contract of
+    `DeviceSampler` holds.
+
+    On GPU with the extension, `state` is ONE fp64 [N,2] tensor (theta,
+    theta_dot) updated in place, and `step`/`reset` are one kernel each
+    (`pendulum_env_step` / `pendulum_env_reset`, env_kernels.hip), so
+    captured graphs and the persistent rollout kernel
+    (`ops/fused_rollout.py::GraphedPendulumRollout`) read and write the same
+    storage the eager path uses.  Assigning `env.state = t` there copies into
+    that storage.  On the CPU the same arithmetic runs as torch fp64 ops.
+
+    Only the init-state RNG stream differs from the numpy env, and it is not
+    the same stream on both devices: Philox keyed by (`_philox_seed`,
+    `_philox_offset`, row) on the GPU, the torch generator on the CPU -- the
+    freedom the module docstring grants.  A GPU run seeded as before the
+    env had kernels therefore starts from other init states.
     """
 
-    def __init__(self, num_envs: int, device="cpu"):
+    def __init__(self, num_envs: int, device="cpu", max_episode_steps: Optional[int] = 200):
         from .classic import PendulumEnv
+        from .core import EnvSpec
 
         base = PendulumEnv()
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.observation_space = base.observation_space
         self.action_space = base.action_space
-        self.spec = base.spec
+        self.spec = EnvSpec("Pendulum-v1", max_episode_steps=max_episode_steps)
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
-        self.state: Optional[Tensor] = None  # [N, 2] float64: theta, theta_dot
+        # [N, 2] float64: theta, theta_dot.  GPU: allocated once, in place
+        self._state: Optional[Tensor] = None
+        if self.device.type == "cuda":
+            self._state = torch.zeros(self.num_envs, 2, dtype=torch.float64,
+                                      device=self.device)
         self._elapsed = 0
+        # same salt as DeviceVectorEnv: decorrelates the env stream from the
+        # policy's action-sampling stream keyed on the same torch seed
+        self._philox_seed = (torch.initial_seed() ^ 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+        self._philox_offset = 0
+
+    @property
+    def state(self) -> Optional[Tensor]:
+        return self._state
+
+    @state.setter
+    def state(self, value: Optional[Tensor]) -> None:
+        if self._state is not None and self._state.is_cuda and value is not None:
+            self._state.copy_(value)  # graphs hold this storage
+        else:
+            self._state = value
 
     def seed(self, seed: Optional[int]) -> None:
         if seed is not None:
             self._gen.manual_seed(int(seed))
+            self._philox_seed = (int(seed) ^ 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+            self._philox_offset = 0
             self.action_space.seed(seed + 1000)
+
+    def _wants_hip(self) -> bool:
+        from rl_replicas_amd import ops
+
+        return self.device.type == "cuda" and ops.wants_hip(self._state)
 
     def _init_state(self) -> Tensor:
         u = torch.rand(self.num_envs, 2, generator=self._gen, device=self.device,
@@ -183,17 +222,54 @@ class DevicePendulumEnv:
                                               dtype=torch.float64)
 
     def _obs(self) -> Tensor:
+        if self._wants_hip():
+            from rl_replicas_amd import ops
+
+            return ops._load_extension().pendulum_env_reset(self._state, 0, 0, draw=False)
         th, thdot = self.state[:, 0], self.state[:, 1]
         return torch.stack([torch.cos(th), torch.sin(th), thdot], dim=1).float()
 
     def reset(self, *, seed: Optional[int] = None) -> Tensor:
         if seed is not None:
             self.seed(seed)
-        self.state = self._init_state()
         self._elapsed = 0
+        if self._wants_hip():
+            from rl_replicas_amd import ops
+
+            obs = ops._load_extension().pendulum_env_reset(
+                self._state, self._philox_seed, self._philox_offset
+            )
+            self._philox_offset += 1
+            return obs
+        self.state = self._init_state()
         return self._obs()
 
     def step(self, actions: Tensor) -> Tuple[Tensor, Tensor, bool, Tensor]:
+        """-> (obs [N,3], reward [N], truncated: host bool, final_obs [N,3]).
+
+        On truncation all instances autoreset; `obs` is post-reset,
+        `final_obs` the true successor (GAE bootstrap)."""
+        if self._wants_hip():
+            from rl_replicas_amd import ops
+
+            self._elapsed += 1
+            truncated = (
+                self.spec.max_episode_steps is not None
+                and self._elapsed >= self.spec.max_episode_steps
+            )
+            # ONE kernel: clamp + cost + Euler step (+ the autoreset draw on
+            # the lockstep horizon step) + the fp32 observations
+            obs, reward, final_obs = ops._load_extension().pendulum_env_step(
+                self._state,
+                actions.to(device=self.device, dtype=torch.float32)
+                .reshape(self.num_envs, -1)[:, :1].contiguous(),
+                truncated, self._philox_seed, self._philox_offset,
+            )
+            self._philox_offset += 1
+            if truncated:
+                self._elapsed = 0
+            return obs, reward, truncated, final_obs
+
         import math
 
         th, thdot = self.state[:, 0], self.state[:, 1]

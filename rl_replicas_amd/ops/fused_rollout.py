@@ -34,6 +34,12 @@ path): termination, truncation and autoreset are decided in-kernel per
 instance, so there are no cut patterns, and the persistent kernel is
 `cartpole_rollout_fused` (`cartpole_fused_eligible`).
 
+`GraphedPendulumRollout` is the construction for a GaussianPolicy on
+`DevicePendulumEnv` (DeviceSampler): lockstep like the synthetic envs, so
+graphs are keyed by the cut pattern, but the carry is the env's own fp64
+`state` as with CartPole; the persistent kernel is
+`pendulum_rollout_fused` (`pendulum_fused_eligible`).
+
 No reference counterpart (the reference samples one env serially on
 the host, batch_sampler.py:55-99).
 """
@@ -282,3 +288,126 @@ class GraphedCartPoleRollout:
 
     def replay(self) -> None:
         self.loop.replay()
+
+
+# ---------------------------------------------------------------------------
+# Gaussian policy on the device Pendulum env (DeviceSampler)
+# ---------------------------------------------------------------------------
+def pendulum_supported(policy, env) -> bool:
+    """A GaussianPolicy over an MLP on a GPU DevicePendulumEnv, with the
+    extension present and graphs enabled."""
+    from rl_replicas_amd.envs.device import DevicePendulumEnv
+
+    if not (isinstance(env, DevicePendulumEnv) and env.device.type == "cuda"
+            and ops.hip_available() and fop._graphs_common(None)
+            and fop._policy_kind(policy) == "gaussian"):
+        return False
+    mlp = fop._mlp_of(policy)
+    return mlp is not None and _extract_layers(mlp) is not None
+
+
+def pendulum_fused_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
+    """Whether the epoch runs as ONE persistent kernel (pendulum_rollout_fused,
+    pendulum_rollout_kernels.hip) instead of steps x 3 kernels: fp32 compute
+    and weights, a net [3, ..., 1] with every width <= 64, one log_std, the
+    cut list and the net image within the kernel's limits.
+    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    import os
+
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
+        return False
+    if ops.compute_bf16() != 0:
+        return False
+    ext = ops._load_extension()
+    weights, _, _ = _extract_layers(fop._mlp_of(policy))
+    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
+    max_layers, max_width, max_cuts, max_lds = ext.pendulum_rollout_fused_limits()
+    if (len(weights) > max_layers or max(dims) > max_width or dims[0] != 3
+            or dims[-1] != 1 or policy.log_std.numel() != 1
+            or len(cuts) > max_cuts):
+        return False
+    if any(t.dtype != torch.float32 for t in (*weights, policy.log_std)):
+        return False
+    return ext.pendulum_rollout_fused_lds_bytes(dims) <= max_lds
+
+
+class GraphedPendulumRollout:
+    """One captured epoch on a DevicePendulumEnv: [pendulum_env_reset | the
+    observation of the carried state] + steps x (mlp_forward ->
+    gaussian_sample -> pendulum_env_step) + counter bump; or, when
+    `pendulum_fused_eligible`, pendulum_rollout_fused + counter bump.
+
+    Pendulum is lockstep, so the graph is keyed (steps, cuts,
+    start_with_reset) like `GraphedRollout`.  The carry between epochs is
+    the env's own fp64 `state`, read and written in place; the fp32
+    observation rows are derived from it.  Philox offsets (both bodies):
+    policy sample and autoreset of step t at `t + ctr` (policy seed / env
+    seed), epoch reset at `steps + ctr`; the last node advances the counter
+    by steps + 1."""
+
+    def __init__(self, policy, env, steps: int, cuts: Tuple[int, ...],
+                 start_with_reset: bool, ctr: torch.Tensor):
+        ext = ops._load_extension()
+        N = env.num_envs
+        dev = env.device
+        self.env = env
+        self.steps = steps
+        self.cuts = list(cuts)
+        self.start_with_reset = start_with_reset
+        self.obs_full = torch.zeros(steps + 1, N, 3, device=dev)
+        self.act_buf = torch.zeros(steps, N, 1, device=dev)
+        self.rew_buf = torch.zeros(steps, N, device=dev)
+        self.cut_final = torch.zeros(max(len(cuts), 1), N, 3, device=dev)
+        self.ctr = ctr
+        policy_seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
+        env_seed = env._philox_seed
+        state = env.state  # the env's in-place carry
+        weights, biases, acts = _extract_layers(fop._mlp_of(policy))
+        log_std = policy.log_std
+        cset = {c: j for j, c in enumerate(cuts)}
+        compute_bf16 = ops.compute_bf16()
+
+        self.fused = pendulum_fused_eligible(policy, env, cuts)
+
+        def body_fused():
+            ext.pendulum_rollout_fused(
+                list(weights), list(biases), acts, log_std.data, policy_seed,
+                env_seed, list(cuts), start_with_reset, self.ctr, state,
+                self.obs_full, self.act_buf, self.rew_buf, self.cut_final,
+            )
+            ext.counter_add_(self.ctr, steps + 1)
+
+        # non-cut steps' successor rows equal obs_full[t + 1]; the kernel
+        # still writes them somewhere
+        fin_scratch = torch.zeros(N, 3, device=dev)
+
+        def body():
+            ext.pendulum_env_reset(state, env_seed, steps, self.ctr,
+                                   self.obs_full[0], start_with_reset)
+            for t in range(steps):
+                mean = ext.mlp_forward(self.obs_full[t], list(weights),
+                                       list(biases), acts, False, compute_bf16)[0]
+                ext.gaussian_sample(mean, log_std.data, policy_seed, t, -1.0,
+                                    -1.0, self.ctr, self.act_buf[t])
+                do_reset = t in cset
+                ext.pendulum_env_step(
+                    state, self.act_buf[t], do_reset, env_seed, t, self.ctr,
+                    self.obs_full[t + 1],
+                    self.cut_final[cset[t]] if do_reset else fin_scratch,
+                    self.rew_buf[t],
+                )
+            # past every offset used: sample/autoreset t (t<steps), reset steps
+            ext.counter_add_(self.ctr, steps + 1)
+
+        # warmup advances ctr and the env carry; snapshot/restore so the
+        # first replay starts exactly where the eager world left off
+        self.loop = fop._CapturedLoop(body_fused if self.fused else body,
+                                      [self.ctr, state])
+
+    def replay(self) -> None:
+        self.loop.replay()
+
+    def final_tensors(self) -> List[torch.Tensor]:
+        """Per-cut bootstrap observations, in cut order."""
+        return [self.cut_final[j] for j in range(len(self.cuts))]

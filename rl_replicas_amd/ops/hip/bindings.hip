@@ -98,6 +98,16 @@ __global__ void cartpole_env_reset_kernel(double* state, int* elapsed, float* ob
                                           const unsigned long long* offset_ptr);
 size_t cartpole_rollout_fused_lds_bytes(const int* dims, int n_layers);
 void launch_cartpole_rollout_fused(const CartPoleRolloutArgs& a, hipStream_t stream);
+__global__ void pendulum_env_step_kernel(double* state, const float* actions,
+                                         float* obs, float* final_obs,
+                                         float* reward, int N, int do_reset,
+                                         uint64_t seed, uint64_t offset,
+                                         const unsigned long long* offset_ptr);
+__global__ void pendulum_env_reset_kernel(double* state, float* obs, int N,
+                                          int draw, uint64_t seed, uint64_t offset,
+                                          const unsigned long long* offset_ptr);
+size_t pendulum_rollout_fused_lds_bytes(const int* dims, int n_layers);
+void launch_pendulum_rollout_fused(const PendulumRolloutArgs& a, hipStream_t stream);
 __global__ void synthetic_env_step_kernel(const float* state, const float* actions,
                                           const float* A, const float* Bm,
                                           const float* w, float* s_out,
@@ -1138,6 +1148,63 @@ torch::Tensor cartpole_env_reset(torch::Tensor state, torch::Tensor elapsed,
   return obs;
 }
 
+// Pendulum carry tensor: state fp64 [N,2]
+static int check_pendulum_carry(const torch::Tensor& state) {
+  TORCH_CHECK(state.is_cuda() && state.is_contiguous() &&
+                  state.scalar_type() == torch::kFloat64 && state.dim() == 2 &&
+                  state.size(1) == 2 && state.size(0) >= 1,
+              "state must be a contiguous float64 CUDA tensor [N, 2]");
+  return (int)state.size(0);
+}
+
+// -> {obs, reward, final_obs}; state is updated in place.  do_reset: the
+// lockstep truncation step (every instance draws a fresh init state)
+std::vector<torch::Tensor> pendulum_env_step(
+    torch::Tensor state, torch::Tensor actions, bool do_reset, int64_t seed,
+    int64_t offset, c10::optional<torch::Tensor> offset_ctr,
+    c10::optional<torch::Tensor> obs_opt, c10::optional<torch::Tensor> final_opt,
+    c10::optional<torch::Tensor> reward_opt) {
+  const int N = check_pendulum_carry(state);
+  check_out(actions, torch::kFloat32, N, "actions");
+  if (obs_opt.has_value()) check_out(*obs_opt, torch::kFloat32, (int64_t)N * 3, "obs");
+  if (final_opt.has_value())
+    check_out(*final_opt, torch::kFloat32, (int64_t)N * 3, "final_obs");
+  if (reward_opt.has_value()) check_out(*reward_opt, torch::kFloat32, N, "reward");
+  const unsigned long long* ctr = ctr_ptr(offset_ctr);
+  const auto f32 = state.options().dtype(torch::kFloat32);
+  auto obs = obs_opt.has_value() ? *obs_opt : torch::empty({N, 3}, f32);
+  auto fin = final_opt.has_value() ? *final_opt : torch::empty({N, 3}, f32);
+  auto reward = reward_opt.has_value() ? *reward_opt : torch::empty({N}, f32);
+  hipLaunchKernelGGL(pendulum_env_step_kernel,
+                     dim3(std::min(256, (N + 255) / 256)), dim3(256), 0,
+                     current_stream(), state.data_ptr<double>(),
+                     actions.data_ptr<float>(), obs.data_ptr<float>(),
+                     fin.data_ptr<float>(), reward.data_ptr<float>(), N,
+                     do_reset ? 1 : 0, (uint64_t)seed, (uint64_t)offset, ctr);
+  HIP_OK(hipGetLastError());
+  return {obs, reward, fin};
+}
+
+// fresh init states into `state` (draw) or only the observation of the
+// states as they stand (!draw); -> obs [N,3]
+torch::Tensor pendulum_env_reset(torch::Tensor state, int64_t seed, int64_t offset,
+                                 c10::optional<torch::Tensor> offset_ctr,
+                                 c10::optional<torch::Tensor> obs_opt, bool draw) {
+  const int N = check_pendulum_carry(state);
+  if (obs_opt.has_value()) check_out(*obs_opt, torch::kFloat32, (int64_t)N * 3, "obs");
+  const unsigned long long* ctr = ctr_ptr(offset_ctr);
+  auto obs = obs_opt.has_value()
+                 ? *obs_opt
+                 : torch::empty({N, 3}, state.options().dtype(torch::kFloat32));
+  hipLaunchKernelGGL(pendulum_env_reset_kernel,
+                     dim3(std::min(256, (N + 255) / 256)), dim3(256), 0,
+                     current_stream(), state.data_ptr<double>(),
+                     obs.data_ptr<float>(), N, draw ? 1 : 0, (uint64_t)seed,
+                     (uint64_t)offset, ctr);
+  HIP_OK(hipGetLastError());
+  return obs;
+}
+
 std::vector<torch::Tensor> synthetic_env_step(torch::Tensor state,
                                               torch::Tensor actions,
                                               torch::Tensor A, torch::Tensor B,
@@ -1809,7 +1876,94 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
   HIP_OK(hipGetLastError());
 }
 
+// dims = [3, hidden..., 1] of the policy net
+int64_t pendulum_rollout_fused_lds_bytes_py(std::vector<int64_t> dims) {
+  const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
+  return (int64_t)pendulum_rollout_fused_lds_bytes(n.dims, n.L);
+}
+
+// whole-epoch Pendulum rollout in one launch (pendulum_rollout_kernels.hip):
+// writes obs_full[0..steps], act_buf, rew_buf, cut_final[j] for cuts[j] and
+// the env carry; reads the RNG counter, never advances it (counter_add_
+// follows).  Shares the CartPole kernel's LDS budget.
+void pendulum_rollout_fused(std::vector<torch::Tensor> weights,
+                            std::vector<torch::Tensor> biases,
+                            std::vector<int64_t> acts, torch::Tensor log_std,
+                            int64_t policy_seed, int64_t env_seed,
+                            std::vector<int64_t> cuts, bool start_with_reset,
+                            torch::Tensor ctr, torch::Tensor state,
+                            torch::Tensor obs_full, torch::Tensor act_buf,
+                            torch::Tensor rew_buf, torch::Tensor cut_final) {
+  const NetLayout net = net_layout(3, weights, biases, acts, ROLLOUT_MAX_WIDTH);
+  const int L = net.L;
+  PendulumRolloutArgs a{};
+  a.N = check_pendulum_carry(state);
+  TORCH_CHECK(net.dims[L] == 1, "pendulum_rollout_fused: the policy head must be 1 wide");
+  check_f32_gpu(log_std, "log_std");
+  TORCH_CHECK(log_std.numel() == 1, "pendulum_rollout_fused: log_std must have 1 element");
+  check_f32_gpu(obs_full, "obs_full");
+  TORCH_CHECK(obs_full.dim() == 3 && obs_full.size(0) >= 2 &&
+                  obs_full.size(1) == a.N && obs_full.size(2) == 3,
+              "obs_full must be [steps+1, N, 3]");
+  a.steps = (int)obs_full.size(0) - 1;
+  const int64_t SN = (int64_t)a.steps * a.N;
+  check_out(act_buf, torch::kFloat32, SN, "act_buf");
+  check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
+  a.n_cuts = (int)cuts.size();
+  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "pendulum_rollout_fused: too many cuts");
+  check_f32_gpu(cut_final, "cut_final");
+  TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
+                  cut_final.size(1) == a.N && cut_final.size(2) == 3,
+              "cut_final must be [n_cuts, N, 3]");
+  for (int c = 0; c < a.n_cuts; ++c) {
+    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < a.steps, "cut step out of range");
+    a.cut_step[c] = (int)cuts[c];
+  }
+  fill_net(a, net, weights, biases, acts);
+  TORCH_CHECK(pendulum_rollout_fused_lds_bytes(a.dims, L) <= CARTPOLE_ROLLOUT_MAX_LDS,
+              "pendulum_rollout_fused: net image exceeds the LDS budget");
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.log_std = log_std.data_ptr<float>();
+  a.state = state.data_ptr<double>();
+  a.obs_full = obs_full.data_ptr<float>();
+  a.act_buf = act_buf.data_ptr<float>();
+  a.rew_buf = rew_buf.data_ptr<float>();
+  a.cut_final = cut_final.data_ptr<float>();
+  a.start_with_reset = start_with_reset ? 1 : 0;
+  a.policy_seed = (uint64_t)policy_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_pendulum_rollout_fused(a, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("pendulum_rollout_fused", &pendulum_rollout_fused,
+        "whole-epoch Pendulum rollout in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"),
+        py::arg("log_std"), py::arg("policy_seed"), py::arg("env_seed"),
+        py::arg("cuts"), py::arg("start_with_reset"), py::arg("ctr"),
+        py::arg("state"), py::arg("obs_full"), py::arg("act_buf"),
+        py::arg("rew_buf"), py::arg("cut_final"));
+  m.def("pendulum_rollout_fused_lds_bytes", &pendulum_rollout_fused_lds_bytes_py,
+        "dynamic LDS of pendulum_rollout_fused for a net [3, ..., 1]");
+  m.def("pendulum_rollout_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
+                                      ROLLOUT_MAX_CUTS, CARTPOLE_ROLLOUT_MAX_LDS};
+        },
+        "(max layers, max width, max cuts, LDS budget in bytes) of "
+        "pendulum_rollout_fused");
+  m.def("pendulum_env_step", &pendulum_env_step,
+        "Pendulum transition + lockstep autoreset (gfx950)", py::arg("state"),
+        py::arg("actions"), py::arg("do_reset"), py::arg("seed"),
+        py::arg("offset"), py::arg("offset_ctr") = py::none(),
+        py::arg("obs") = py::none(), py::arg("final_obs") = py::none(),
+        py::arg("reward") = py::none());
+  m.def("pendulum_env_reset", &pendulum_env_reset,
+        "Pendulum init states, or (draw=False) the observation of `state`",
+        py::arg("state"), py::arg("seed"), py::arg("offset"),
+        py::arg("offset_ctr") = py::none(), py::arg("obs") = py::none(),
+        py::arg("draw") = true);
   m.def("cartpole_rollout_fused", &cartpole_rollout_fused,
         "whole-epoch CartPole rollout in one persistent kernel (gfx950)",
         py::arg("weights"), py::arg("biases"), py::arg("acts"),

@@ -285,6 +285,29 @@ struct CartPoleRolloutArgs {
   uint64_t policy_seed, env_seed;
 };
 
+// persistent Pendulum rollout kernel (pendulum_rollout_kernels.hip): one
+// workgroup carries ROLLOUT_ROWS instances through all `steps` iterations
+// of forward -> Gaussian sample -> transition / lockstep autoreset.
+struct PendulumRolloutArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;
+  const float* log_std;    // [1]
+  double* state;           // [N, 2] env carry (read unless start_with_reset)
+  float* obs_full;         // [steps + 1, N, 3]
+  float* act_buf;          // [steps, N, 1]
+  float* rew_buf;          // [steps, N]
+  float* cut_final;        // [n_cuts, N, 3] pre-reset successors, cut order
+  const unsigned long long* ctr;  // device RNG counter (read once)
+  int cut_step[ROLLOUT_MAX_CUTS];  // ascending
+  int n_cuts;
+  int N, steps;
+  int start_with_reset;
+  uint64_t policy_seed, env_seed;
+};
+
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)
 struct ReplayGatherArgs {
   const float* obs;   // [cap, O] ring storage

@@ -13,7 +13,8 @@
 //
 // CartPole-v1 (DeviceCartPoleEnv) has its own step/reset kernels below:
 // fp64 state, one thread per instance, per-instance termination,
-// truncation and autoreset.
+// truncation and autoreset.  Pendulum-v1 (DevicePendulumEnv) follows: fp64
+// state, one thread per instance, lockstep truncation decided by the host.
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
@@ -99,6 +100,56 @@ __global__ __launch_bounds__(256) void cartpole_env_reset_kernel(
       obs[(long)row * 4 + k] = (float)s[k];
     }
     elapsed[row] = 0;
+  }
+}
+
+// Pendulum-v1, lockstep (no early termination; the host knows the truncation
+// step and passes do_reset): one thread per instance.  state fp64 [N,2] is
+// updated in place; obs is the post-autoreset observation, final_obs the
+// true successor, reward the cost of the pre-step state.
+__global__ __launch_bounds__(256) void pendulum_env_step_kernel(
+    double* __restrict__ state, const float* __restrict__ actions,
+    float* __restrict__ obs, float* __restrict__ final_obs,
+    float* __restrict__ reward, int N, int do_reset, uint64_t seed,
+    uint64_t offset, const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
+    double s[2] = {state[(long)row * 2], state[(long)row * 2 + 1]};
+    float fin[3], ob[3], r;
+    pendulum_env_row(s, actions[row], do_reset, seed, offset, (uint32_t)row, fin,
+                     ob, &r);
+    state[(long)row * 2] = s[0];
+    state[(long)row * 2 + 1] = s[1];
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      obs[(long)row * 3 + k] = ob[k];
+      final_obs[(long)row * 3 + k] = fin[k];
+    }
+    reward[row] = r;
+  }
+}
+
+// fresh Pendulum states for all N instances (draw != 0), or only the
+// observation of the states as they stand (draw == 0)
+__global__ __launch_bounds__(256) void pendulum_env_reset_kernel(
+    double* __restrict__ state, float* __restrict__ obs, int N, int draw,
+    uint64_t seed, uint64_t offset,
+    const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
+    double s[2];
+    if (draw) {
+      pendulum_reset_draw(seed, offset, (uint32_t)row, s);
+      state[(long)row * 2] = s[0];
+      state[(long)row * 2 + 1] = s[1];
+    } else {
+      s[0] = state[(long)row * 2];
+      s[1] = state[(long)row * 2 + 1];
+    }
+    float ob[3];
+    pendulum_obs(s, ob);
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) obs[(long)row * 3 + k] = ob[k];
   }
 }
 

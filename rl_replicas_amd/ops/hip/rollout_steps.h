@@ -1,8 +1,9 @@
 // Per-row arithmetic of one rollout step, shared by the stand-alone
 // kernels (fused_mlp_fwd_f32_t, gaussian_sample_kernel,
 // categorical_sample_kernel, synthetic_env_step_kernel,
-// cartpole_env_step_kernel) and the persistent rollout kernels
-// (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip).  Every caller
+// cartpole_env_step_kernel, pendulum_env_step_kernel) and the persistent
+// rollout kernels (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip,
+// pendulum_rollout_kernels.hip).  Every caller
 // inlines the SAME expressions in the SAME order, so both routes produce
 // the same bytes; the operands may live in global memory or in LDS.
 #pragma once
@@ -196,4 +197,64 @@ DEV_INLINE bool cartpole_env_row(double s[4], int* elapsed, int action,
   #pragma unroll
   for (int k = 0; k < 4; ++k) obs[k] = (float)s[k];
   return done;
+}
+
+// Pendulum-v1 (envs/classic.py::PendulumEnv._step_b): one step of
+// s = (theta, theta_dot) in fp64, the host env's constants and expression
+// order, no contraction.  *reward = (float)(-costs) of the PRE-step state.
+DEV_INLINE void pendulum_row_step(double s[2], float action, float* reward) {
+#pragma clang fp contract(off)
+  constexpr double PI = 3.141592653589793;
+  constexpr double TWO_PI = 2.0 * 3.141592653589793;
+  constexpr double MAX_SPEED = 8.0;
+  constexpr double MAX_TORQUE = 2.0;
+  constexpr double DT = 0.05;
+  const double th = s[0], thdot = s[1];
+  const double u = fmin(fmax((double)action, -MAX_TORQUE), MAX_TORQUE);
+  // numpy's %: the result takes the sign of the (positive) divisor
+  double ang = fmod(th + PI, TWO_PI);
+  if (ang < 0.0) ang = ang + TWO_PI;
+  ang = ang - PI;
+  const double costs = ang * ang + 0.1 * (thdot * thdot) + 0.001 * (u * u);
+  double newthdot = thdot + (15.0 * sin(th) + 3.0 * u) * DT;
+  newthdot = fmin(fmax(newthdot, -MAX_SPEED), MAX_SPEED);
+  const double newth = th + newthdot * DT;
+  s[0] = newth; s[1] = newthdot;
+  *reward = (float)(-costs);
+}
+
+// Pendulum init state: theta strictly inside (-pi, pi), theta_dot strictly
+// inside (-1, 1), from ONE Philox call keyed by (seed, offset, row)
+DEV_INLINE void pendulum_reset_draw(uint64_t seed, uint64_t offset, uint32_t row,
+                                    double out[2]) {
+#pragma clang fp contract(off)
+  constexpr double PI = 3.141592653589793;
+  uint32_t r[4];
+  philox4(seed, offset, row, r);
+  out[0] = -PI + (2.0 * PI) * (((double)r[0] + 0.5) * (1.0 / 4294967296.0));
+  out[1] = -1.0 + 2.0 * (((double)r[1] + 0.5) * (1.0 / 4294967296.0));
+}
+
+// observation (cos theta, sin theta, theta_dot) in fp32
+DEV_INLINE void pendulum_obs(const double s[2], float o[3]) {
+  o[0] = (float)cos(s[0]);
+  o[1] = (float)sin(s[0]);
+  o[2] = (float)s[1];
+}
+
+// one whole env row of the lockstep step: transition, then (do_reset) the
+// autoreset draw.  s is updated in place to the next LIVE state; fin is the
+// true successor observation, obs the post-autoreset one.
+DEV_INLINE void pendulum_env_row(double s[2], float action, int do_reset,
+                                 uint64_t seed, uint64_t offset, uint32_t row,
+                                 float fin[3], float obs[3], float* reward) {
+  pendulum_row_step(s, action, reward);
+  pendulum_obs(s, fin);
+  if (do_reset) {
+    pendulum_reset_draw(seed, offset, row, s);
+    pendulum_obs(s, obs);
+  } else {
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) obs[k] = fin[k];
+  }
 }

@@ -9,9 +9,10 @@ H2D upload entirely.  The only per-epoch D2H is one small readback of
 per-episode returns/lengths for metrics (a few hundred floats).
 
 On GPU with a Gaussian MLP policy the whole epoch rollout is captured
-once into a hipGraph and replayed per epoch (`ops/fused_rollout.py`);
-otherwise an eager loop issues the same kernels.  Both paths produce
-identical episode structure; randomness streams differ (device-counter
+once into a hipGraph and replayed per epoch (`ops/fused_rollout.py`:
+`GraphedRollout` for the synthetic envs, `GraphedPendulumRollout` for
+`DevicePendulumEnv`); otherwise an eager loop issues the same kernels.
+Both paths produce identical episode structure; randomness streams differ (device-counter
 Philox vs host-counter Philox/torch generator), each deterministic
 under its seed.
 
@@ -32,7 +33,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from rl_replicas_amd.envs.device import DeviceVectorEnv
+from rl_replicas_amd.envs.device import DevicePendulumEnv, DeviceVectorEnv
 from rl_replicas_amd.experience import Experience
 from rl_replicas_amd.policies import Policy
 from rl_replicas_amd.samplers.sampler import Sampler
@@ -85,13 +86,18 @@ class DeviceSampler(Sampler):
         # when horizon % steps != 0 the truncation pattern cycles through
         # up to horizon/gcd values — cap the graph cache and serve unseen
         # patterns eagerly instead of capturing without bound
-        graph_ok = fused_rollout.supported(policy, env) and (
+        pendulum = isinstance(env, DevicePendulumEnv)
+        can_graph = (fused_rollout.pendulum_supported(policy, env) if pendulum
+                     else fused_rollout.supported(policy, env))
+        graph_ok = can_graph and (
             (steps, cuts, reset_epoch) in self._graphs or len(self._graphs) < 8
         )
         if graph_ok:
             if first and self.seed is not None:
                 env.seed(self.seed)
-            obs_buf, act_buf, rew_buf, finals = self._sample_graphed(
+            sample_graphed = (self._sample_graphed_pendulum if pendulum
+                              else self._sample_graphed)
+            obs_buf, act_buf, rew_buf, finals = sample_graphed(
                 policy, steps, cuts, reset_epoch
             )
         else:
@@ -126,6 +132,28 @@ class DeviceSampler(Sampler):
         g.replay()
         self._obs = g.obs_full[steps]
         env.state = self._obs
+        return g.obs_full[:steps], g.act_buf, g.rew_buf, g.final_tensors()
+
+    # ------------------------------------------------------------------
+    def _sample_graphed_pendulum(self, policy, steps: int, cuts: Tuple[int, ...],
+                                 reset_epoch: bool):
+        """DevicePendulumEnv: the carry between epochs is the env's own fp64
+        `state`, which the kernels read and write in place; the observation
+        carry is derived from it, so nothing is copied in or out here."""
+        from rl_replicas_amd.ops import fused_rollout
+
+        env = self.env
+        if self._graph_ctr is None:
+            self._graph_ctr = fused_rollout.make_counter(env.device)
+        key = (steps, cuts, reset_epoch)
+        g = self._graphs.get(key)
+        if g is None:
+            g = fused_rollout.GraphedPendulumRollout(
+                policy, env, steps, cuts, reset_epoch, self._graph_ctr
+            )
+            self._graphs[key] = g
+        g.replay()
+        self._obs = g.obs_full[steps]
         return g.obs_full[:steps], g.act_buf, g.rew_buf, g.final_tensors()
 
     # ------------------------------------------------------------------
