@@ -93,8 +93,16 @@ def build_off_policy(env_id: str, seed: int, device: Optional[str], num_envs: in
                      twin: bool, env_mode: str = "cpu"):
     set_seed_for_libraries(seed)
     dev = pick_device(device)
-    env, sampler = make_sampler(env_id, seed, num_envs, is_continuous=True,
-                                env_mode=env_mode, device=dev)
+    buffer = ReplayBuffer(int(1e6), device=dev if dev.startswith("cuda") else None)
+    if env_mode == "device" and env_id == "Pendulum-v1":
+        # the collect phase writes straight into the buffer's ring
+        from rl_replicas_amd.samplers import DeviceReplaySampler
+
+        env = envs.DevicePendulumEnv(num_envs=num_envs, device=dev)
+        sampler = DeviceReplaySampler(env, buffer, seed=seed)
+    else:
+        env, sampler = make_sampler(env_id, seed, num_envs, is_continuous=True,
+                                    env_mode=env_mode, device=dev)
     obs_dim = env.observation_space.shape[0]
     act_dim = env.action_space.shape[0]
 
@@ -107,6 +115,5 @@ def build_off_policy(env_id: str, seed: int, device: Optional[str], num_envs: in
         return QFunction(qnet, ops.make_adam(qnet.parameters(), lr=1e-3))
 
     qs = [make_q() for _ in range(2 if twin else 1)]
-    buffer = ReplayBuffer(int(1e6), device=dev if dev.startswith("cuda") else None)
     evaluator = Evaluator(seed=seed)
     return env, sampler, policy, exploration, qs, buffer, evaluator

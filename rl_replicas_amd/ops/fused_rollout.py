@@ -40,6 +40,13 @@ graphs are keyed by the cut pattern, but the carry is the env's own fp64
 `state` as with CartPole; the persistent kernel is
 `pendulum_rollout_fused` (`pendulum_fused_eligible`).
 
+`GraphedPendulumCollect` is the off-policy construction on
+`DevicePendulumEnv` (DeviceReplaySampler): the behaviour policy is the
+noised deterministic actor or the uniform warm-up draw, and the epoch's
+transitions go straight into a ReplayBuffer's HBM ring at the write
+position the buffer holds on the device; the persistent kernel is
+`pendulum_collect_fused` (`pendulum_collect_fused_eligible`).
+
 No reference counterpart (the reference samples one env serially on
 the host, batch_sampler.py:55-99).
 """
@@ -411,3 +418,239 @@ class GraphedPendulumRollout:
     def final_tensors(self) -> List[torch.Tensor]:
         """Per-cut bootstrap observations, in cut order."""
         return [self.cut_final[j] for j in range(len(self.cuts))]
+
+
+# ---------------------------------------------------------------------------
+# Off-policy replay collection on the device Pendulum env
+# (DeviceReplaySampler)
+# ---------------------------------------------------------------------------
+COLLECT_NOISED = "noised"
+COLLECT_UNIFORM = "uniform"
+_COLLECT_MODE_CODE = {COLLECT_NOISED: 0, COLLECT_UNIFORM: 1}  # common.h
+# salt of the uniform warm-up stream (the noised stream keeps
+# utils._NoisedPolicy's 0x517CC1B727220A95)
+_UNIFORM_SALT = 0x2545F4914F6CDD1D
+_NOISE_SALT = 0x517CC1B727220A95
+
+
+def pendulum_collect_mode(policy, env):
+    """Which behaviour policy of OffPolicyAlgorithm.learn `policy` is:
+    COLLECT_NOISED (a utils._NoisedPolicy over a DeterministicPolicy over an
+    fp32 MLP [3, ..., 1] the fused-MLP kernels take, on the env's device),
+    COLLECT_UNIFORM (a RandomPolicy over the env's one-dimensional Box), or
+    None."""
+    import numpy as np
+
+    from rl_replicas_amd.policies import DeterministicPolicy, RandomPolicy
+    from rl_replicas_amd.utils import _NoisedPolicy
+
+    if isinstance(policy, RandomPolicy):
+        space = policy.action_space
+        own = env.action_space
+        if not all(hasattr(s, "low") and hasattr(s, "high") for s in (space, own)):
+            return None
+        lo, hi = np.asarray(space.low).reshape(-1), np.asarray(space.high).reshape(-1)
+        if (lo.size != 1 or hi.size != 1 or not np.isfinite([lo[0], hi[0]]).all()
+                or lo[0] > hi[0]
+                or not np.array_equal(lo, np.asarray(own.low).reshape(-1))
+                or not np.array_equal(hi, np.asarray(own.high).reshape(-1))):
+            return None
+        return COLLECT_UNIFORM
+    if isinstance(policy, _NoisedPolicy) and isinstance(policy.base_policy,
+                                                        DeterministicPolicy):
+        mlp = fop._mlp_of(policy.base_policy)
+        layers = _extract_layers(mlp) if mlp is not None else None
+        if layers is None or policy.action_noise_scale < 0 or policy.action_limit < 0:
+            return None
+        weights, biases, _ = layers
+        if (int(weights[0].shape[1]) != 3 or int(weights[-1].shape[0]) != 1
+                or any(t.dtype != torch.float32 or t.device != env.state.device
+                       for t in (*weights, *biases))):
+            return None
+        return COLLECT_NOISED
+    return None
+
+
+def pendulum_collect_supported(policy, env, buffer) -> bool:
+    """A behaviour policy of `learn()` on a GPU DevicePendulumEnv whose
+    ReplayBuffer lives on the same device, with the extension present and
+    graphs enabled."""
+    from rl_replicas_amd.envs.device import DevicePendulumEnv
+
+    if not (isinstance(env, DevicePendulumEnv) and env.device.type == "cuda"
+            and ops.hip_available() and fop._graphs_common(None)):
+        return False
+    if buffer is None or buffer.device is None or buffer.device.type != "cuda":
+        return False
+    if env.state is None or torch.empty(0, device=buffer.device).device != env.state.device:
+        return False
+    return pendulum_collect_mode(policy, env) is not None
+
+
+def collect_fused_default() -> bool:
+    """Which body a collect graph takes when RL_REPLICAS_AMD_ROLLOUT_FUSED is
+    unset: the persistent kernel, which beat the multi-kernel body beyond
+    their run-to-run spread at both off-policy shapes and in both modes
+    (profiles/bench_replay_collect_1gpu.json, docs/ARCHITECTURE.md)."""
+    return True
+
+
+def collect_wide_threads() -> int:
+    """Workgroup size of the persistent kernel's wide regime: 1024 (one
+    column tile per wave at width 256), the measured default, or 256 (four
+    tiles per wave) with RL_REPLICAS_AMD_COLLECT_WG=256."""
+    import os
+
+    return 256 if os.environ.get("RL_REPLICAS_AMD_COLLECT_WG", "1024") == "256" else 1024
+
+
+def pendulum_collect_fused_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
+    """Whether a collect epoch runs as ONE persistent kernel
+    (pendulum_collect_fused, pendulum_collect_kernels.hip) instead of the
+    multi-kernel body: fp32 compute and weights, an actor [3, ..., 1] and a
+    cut list within the binding's own limits.
+    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    import os
+
+    default = "1" if collect_fused_default() else "0"
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", default) == "0":
+        return False
+    if ops.compute_bf16() != 0:
+        return False
+    ext = ops._load_extension()
+    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
+    max_layers, max_width, max_cuts, max_lds = ext.pendulum_collect_fused_limits()
+    if len(cuts) > max_cuts:
+        return False
+    # an fp32 actor [3, ..., 1] on the env's device, or no net at all
+    mode = pendulum_collect_mode(policy, env)
+    if mode is None:
+        return False
+    if mode == COLLECT_UNIFORM:
+        return True
+    weights, _, _ = _extract_layers(fop._mlp_of(policy.base_policy))
+    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+    if len(weights) > max_layers or max(dims) > max_width:
+        return False
+    return ext.pendulum_collect_fused_lds_bytes(dims) <= max_lds
+
+
+class GraphedPendulumCollect:
+    """One captured off-policy collect epoch on a DevicePendulumEnv, written
+    straight into a ReplayBuffer's HBM ring at the write position the
+    buffer holds on the device.
+
+    Fused body (`pendulum_collect_fused_eligible`): pendulum_collect_fused,
+    ring_advance_, counter_add_.  Multi-kernel body: pendulum_env_reset,
+    steps x ([mlp_forward -> gaussian_sample with noise scale / limit] |
+    uniform_sample, then pendulum_env_step), replay_scatter, ring_advance_,
+    counter_add_.  Both write the same bytes.
+
+    Keyed (steps, cuts, start_with_reset, mode) by the sampler.  Philox
+    offsets (both bodies): action and autoreset of step t at `t + ctr`
+    (action seed / env seed), epoch reset at `steps + ctr`; the counter
+    advances by steps + 1.  Warm-up leaves no trace: the counter, the env
+    carry and both ring scalars are restored by `_CapturedLoop`, the ring
+    rows the warm-up runs wrote are put back here."""
+
+    def __init__(self, policy, env, buffer, steps: int, cuts: Tuple[int, ...],
+                 start_with_reset: bool, mode: str, ctr: torch.Tensor):
+        ext = ops._load_extension()
+        N = env.num_envs
+        dev = env.device
+        n = N * steps
+        cap = buffer.buffer_size
+        assert n <= cap
+        self.env = env
+        self.buffer = buffer
+        self.steps = steps
+        self.cuts = list(cuts)
+        self.start_with_reset = start_with_reset
+        self.mode = mode
+        self.ctr = ctr
+        self.n_segs = len(cuts) + (1 if not cuts or cuts[-1] != steps - 1 else 0)
+        # the one read-back of an epoch
+        self.seg_returns = torch.zeros(N, self.n_segs, device=dev)
+        storage, write_dev, size_dev = buffer.device_ring(3, (1,))
+        state = env.state  # the env's in-place carry
+        env_seed = env._philox_seed
+        base_seed = torch.initial_seed()
+        cset = {c: j for j, c in enumerate(cuts)}
+        compute_bf16 = ops.compute_bf16()
+        low = float(env.action_space.low.reshape(-1)[0])
+        high = float(env.action_space.high.reshape(-1)[0])
+        if mode == COLLECT_NOISED:
+            weights, biases, acts = _extract_layers(fop._mlp_of(policy.base_policy))
+            weights, biases = list(weights), list(biases)
+            action_seed = (base_seed ^ _NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
+            noise_scale = float(policy.action_noise_scale)
+            limit = float(policy.action_limit)
+            dummy_log_std = torch.zeros(1, device=dev)
+        else:
+            weights, biases, acts = [], [], []
+            action_seed = (base_seed ^ _UNIFORM_SALT) & 0x7FFFFFFFFFFFFFFF
+            noise_scale, limit = 0.0, 0.0
+
+        self.fused = pendulum_collect_fused_eligible(policy, env, cuts)
+        wide_threads = collect_wide_threads()
+
+        if self.fused:
+            self.last_obs = torch.zeros(N, 3, device=dev)
+
+            def body():
+                ext.pendulum_collect_fused(
+                    weights, biases, acts, _COLLECT_MODE_CODE[mode], noise_scale,
+                    limit, low, high, action_seed, env_seed, list(cuts),
+                    start_with_reset, self.ctr, state, steps, storage, write_dev,
+                    size_dev, self.seg_returns, self.last_obs, wide_threads,
+                )
+                ext.ring_advance_(write_dev, size_dev, n, cap)
+                ext.counter_add_(self.ctr, steps + 1)
+        else:
+            self.obs_full = torch.zeros(steps + 1, N, 3, device=dev)
+            self.act_buf = torch.zeros(steps, N, 1, device=dev)
+            self.rew_buf = torch.zeros(steps, N, device=dev)
+            self.cut_final = torch.zeros(max(len(cuts), 1), N, 3, device=dev)
+            self.last_obs = self.obs_full[steps]
+            cut_slot = torch.tensor([cset.get(t, -1) for t in range(steps)],
+                                    dtype=torch.int32, device=dev)
+            fin_scratch = torch.zeros(N, 3, device=dev)
+
+            def body():
+                ext.pendulum_env_reset(state, env_seed, steps, self.ctr,
+                                       self.obs_full[0], start_with_reset)
+                for t in range(steps):
+                    if mode == COLLECT_NOISED:
+                        mean = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                               acts, False, compute_bf16)[0]
+                        ext.gaussian_sample(mean, dummy_log_std, action_seed, t,
+                                            noise_scale, limit, self.ctr,
+                                            self.act_buf[t])
+                    else:
+                        ext.uniform_sample(self.act_buf[t], low, high, action_seed,
+                                           t, self.ctr)
+                    do_reset = t in cset
+                    ext.pendulum_env_step(
+                        state, self.act_buf[t], do_reset, env_seed, t, self.ctr,
+                        self.obs_full[t + 1],
+                        self.cut_final[cset[t]] if do_reset else fin_scratch,
+                        self.rew_buf[t],
+                    )
+                ext.replay_scatter(self.obs_full, self.act_buf, self.rew_buf,
+                                   self.cut_final, cut_slot, len(cuts), storage,
+                                   write_dev, size_dev, self.seg_returns)
+                ext.ring_advance_(write_dev, size_dev, n, cap)
+                # past every offset used: action/autoreset t (t<steps), reset steps
+                ext.counter_add_(self.ctr, steps + 1)
+
+        # the two warm-up runs write ring rows [write, write + 2n): keep what
+        # they held, so warm-up never costs a stored transition
+        touched = (buffer._write + torch.arange(min(2 * n, cap), device=dev)) % cap
+        kept = [t[touched] for t in storage]
+        self.loop = fop._CapturedLoop(body, [self.ctr, state, write_dev, size_dev])
+        for t, k in zip(storage, kept):
+            t[touched] = k
+
+    def replay(self) -> None:
+        self.loop.replay()
+        self.buffer.advance_host(self.env.num_envs * self.steps)

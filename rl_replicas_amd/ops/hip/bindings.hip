@@ -108,6 +108,16 @@ __global__ void pendulum_env_reset_kernel(double* state, float* obs, int N,
                                           const unsigned long long* offset_ptr);
 size_t pendulum_rollout_fused_lds_bytes(const int* dims, int n_layers);
 void launch_pendulum_rollout_fused(const PendulumRolloutArgs& a, hipStream_t stream);
+bool pendulum_collect_fused_is_wide(const int* dims, int n_layers);
+size_t pendulum_collect_fused_lds_bytes(const int* dims, int n_layers);
+void launch_pendulum_collect_fused(const PendulumCollectArgs& a, int wide_threads,
+                                   hipStream_t stream);
+__global__ void uniform_sample_kernel(float* out, int total, float low, float high,
+                                      uint64_t seed, uint64_t offset,
+                                      const unsigned long long* offset_ptr);
+__global__ void replay_scatter_kernel(ReplayScatterArgs a);
+__global__ void ring_advance_kernel(long long* write, long long* size,
+                                    unsigned long long n, unsigned long long cap);
 __global__ void synthetic_env_step_kernel(const float* state, const float* actions,
                                           const float* A, const float* Bm,
                                           const float* w, float* s_out,
@@ -1936,7 +1946,239 @@ void pendulum_rollout_fused(std::vector<torch::Tensor> weights,
   HIP_OK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// Pendulum replay collection: device-side ring writes
+// ---------------------------------------------------------------------------
+// The replay ring handed to a collect kernel: storage = [observations [cap,3],
+// actions [cap,1], rewards [cap], next_observations [cap,3], dones [cap]],
+// all contiguous fp32 on `dev`, both scalars 1-element int64 there, and room
+// for the epoch's n transitions without a slot written twice.
+static ReplayRing check_ring(const std::vector<torch::Tensor>& storage,
+                             const torch::Tensor& write_dev,
+                             const torch::Tensor& size_dev, int64_t n,
+                             const torch::Device& dev) {
+  TORCH_CHECK(storage.size() == 5,
+              "ring storage must be [obs, act, rew, next_obs, dones]");
+  static const char* names[5] = {"ring observations", "ring actions", "ring rewards",
+                                 "ring next_observations", "ring dones"};
+  for (int i = 0; i < 5; ++i) {
+    check_f32_gpu(storage[i], names[i]);
+    TORCH_CHECK(storage[i].device() == dev, names[i], " is on another device");
+    TORCH_CHECK(storage[i].dim() >= 1, names[i], " must have a slot dimension");
+  }
+  const int64_t cap = storage[2].numel();
+  TORCH_CHECK(cap >= 1, "empty ring");
+  const int64_t per_slot[5] = {3, 1, 1, 3, 1};
+  for (int i = 0; i < 5; ++i)
+    TORCH_CHECK(storage[i].size(0) == cap && storage[i].numel() == cap * per_slot[i],
+                names[i], " must hold ", per_slot[i], " floats per ring slot");
+  for (const torch::Tensor* s : {&write_dev, &size_dev})
+    TORCH_CHECK(s->scalar_type() == torch::kInt64 && s->is_cuda() &&
+                    s->numel() == 1 && s->device() == dev,
+                "ring scalars must be 1-element int64 tensors on the ring's device");
+  TORCH_CHECK(n >= 1 && n <= cap, "an epoch of ", n,
+              " transitions does not fit a ring of ", cap);
+  ReplayRing r{};
+  r.obs = storage[0].data_ptr<float>();
+  r.act = storage[1].data_ptr<float>();
+  r.rew = storage[2].data_ptr<float>();
+  r.nxt = storage[3].data_ptr<float>();
+  r.dn = storage[4].data_ptr<float>();
+  r.write = reinterpret_cast<const long long*>(write_dev.data_ptr<int64_t>());
+  r.cap = (unsigned long long)cap;
+  return r;
+}
+
+// segments of a lockstep epoch: one per cut, plus the open one when the
+// last step is no cut
+static int epoch_segments(const std::vector<int64_t>& cuts, int64_t steps) {
+  return (int)cuts.size() + ((cuts.empty() || cuts.back() != steps - 1) ? 1 : 0);
+}
+
+// dims = [3, hidden..., 1] of the actor
+int64_t pendulum_collect_fused_lds_bytes_py(std::vector<int64_t> dims) {
+  const NetLayout n = net_layout(dims, MLP_MAX_WIDTH);
+  return (int64_t)pendulum_collect_fused_lds_bytes(n.dims, n.L);
+}
+
+// whole-epoch Pendulum replay collection in one launch
+// (pendulum_collect_kernels.hip): writes the epoch's N * steps transitions
+// into the ring at the device-held write position, seg_returns, last_obs and
+// the env carry; reads the RNG counter and the ring scalars, never advances
+// them (ring_advance_ and counter_add_ follow).  mode COLLECT_UNIFORM takes
+// no net.  wide_threads: workgroup size of the wide regime, 256 or 1024.
+void pendulum_collect_fused(std::vector<torch::Tensor> weights,
+                            std::vector<torch::Tensor> biases,
+                            std::vector<int64_t> acts, int64_t mode,
+                            double noise_scale, double limit, double low,
+                            double high, int64_t action_seed, int64_t env_seed,
+                            std::vector<int64_t> cuts, bool start_with_reset,
+                            torch::Tensor ctr, torch::Tensor state, int64_t steps,
+                            std::vector<torch::Tensor> storage,
+                            torch::Tensor write_dev, torch::Tensor size_dev,
+                            torch::Tensor seg_returns, torch::Tensor last_obs,
+                            int64_t wide_threads) {
+  PendulumCollectArgs a{};
+  a.N = check_pendulum_carry(state);
+  TORCH_CHECK(steps >= 1 && steps <= (1 << 24), "steps out of range");
+  a.steps = (int)steps;
+  a.ring = check_ring(storage, write_dev, size_dev, (int64_t)a.N * steps,
+                      state.device());
+  TORCH_CHECK(mode == COLLECT_NOISED || mode == COLLECT_UNIFORM, "unknown mode");
+  a.mode = (int)mode;
+  if (mode == COLLECT_NOISED) {
+    const NetLayout net = net_layout(3, weights, biases, acts, MLP_MAX_WIDTH);
+    TORCH_CHECK(net.dims[net.L] == 1,
+                "pendulum_collect_fused: the actor head must be 1 wide");
+    for (const auto& t : weights)
+      TORCH_CHECK(t.device() == state.device(), "actor is on another device");
+    for (const auto& t : biases)
+      TORCH_CHECK(t.device() == state.device(), "actor is on another device");
+    TORCH_CHECK(noise_scale >= 0.0 && limit >= 0.0,
+                "pendulum_collect_fused: noise_scale and limit must be >= 0");
+    fill_net(a, net, weights, biases, acts);
+  } else {
+    TORCH_CHECK(weights.empty() && biases.empty() && acts.empty(),
+                "pendulum_collect_fused: uniform mode takes no net");
+    TORCH_CHECK(low <= high, "pendulum_collect_fused: low > high");
+  }
+  TORCH_CHECK(pendulum_collect_fused_lds_bytes(a.dims, a.n_layers) <= MLP_LDS_BUDGET,
+              "pendulum_collect_fused: net image exceeds the LDS budget");
+  TORCH_CHECK(wide_threads == 256 || wide_threads == 1024,
+              "pendulum_collect_fused: wide_threads must be 256 or 1024");
+  a.n_cuts = (int)cuts.size();
+  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "pendulum_collect_fused: too many cuts");
+  for (int c = 0; c < a.n_cuts; ++c) {
+    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < steps, "cut step out of range");
+    TORCH_CHECK(c == 0 || cuts[c] > cuts[c - 1], "cuts must be ascending");
+    a.cut_step[c] = (int)cuts[c];
+  }
+  a.n_segs = epoch_segments(cuts, steps);
+  check_out(seg_returns, torch::kFloat32, (int64_t)a.N * a.n_segs, "seg_returns");
+  check_out(last_obs, torch::kFloat32, (int64_t)a.N * 3, "last_obs");
+  TORCH_CHECK(seg_returns.device() == state.device() &&
+                  last_obs.device() == state.device(),
+              "seg_returns / last_obs are on another device");
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.state = state.data_ptr<double>();
+  a.seg_returns = seg_returns.data_ptr<float>();
+  a.last_obs = last_obs.data_ptr<float>();
+  a.start_with_reset = start_with_reset ? 1 : 0;
+  a.noise_scale = (float)noise_scale;
+  a.limit = (float)limit;
+  a.low = (float)low;
+  a.high = (float)high;
+  a.action_seed = (uint64_t)action_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_pendulum_collect_fused(a, (int)wide_threads, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
+// out[i] = low + (high - low) * u, u in (0, 1] keyed by (seed, offset, i)
+void uniform_sample(torch::Tensor out, double low, double high, int64_t seed,
+                    int64_t offset, c10::optional<torch::Tensor> offset_ctr) {
+  check_f32_gpu(out, "out");
+  TORCH_CHECK(low <= high, "uniform_sample: low > high");
+  TORCH_CHECK(out.numel() < (1LL << 31), "uniform_sample: out too large");
+  const int total = (int)out.numel();
+  if (total == 0) return;
+  hipLaunchKernelGGL(uniform_sample_kernel,
+                     dim3(std::min(256, (total + 255) / 256)), dim3(256), 0,
+                     current_stream(), out.data_ptr<float>(), total, (float)low,
+                     (float)high, (uint64_t)seed, (uint64_t)offset,
+                     ctr_ptr(offset_ctr));
+  HIP_OK(hipGetLastError());
+}
+
+// the multi-kernel body's ring write: the epoch buffers of steps x (action
+// -> pendulum_env_step) into the slots pendulum_collect_fused writes.
+// cut_slot [steps] int32: index into cut_final on cut steps, -1 elsewhere.
+void replay_scatter(torch::Tensor obs_full, torch::Tensor act_buf,
+                    torch::Tensor rew_buf, torch::Tensor cut_final,
+                    torch::Tensor cut_slot, int64_t n_cuts,
+                    std::vector<torch::Tensor> storage, torch::Tensor write_dev,
+                    torch::Tensor size_dev, torch::Tensor seg_returns) {
+  check_f32_gpu(obs_full, "obs_full");
+  TORCH_CHECK(obs_full.dim() == 3 && obs_full.size(0) >= 2 && obs_full.size(1) >= 1 &&
+                  obs_full.size(2) == 3,
+              "obs_full must be [steps+1, N, 3]");
+  ReplayScatterArgs a{};
+  a.steps = (int)obs_full.size(0) - 1;
+  a.N = (int)obs_full.size(1);
+  const int64_t SN = (int64_t)a.steps * a.N;
+  a.ring = check_ring(storage, write_dev, size_dev, SN, obs_full.device());
+  check_out(act_buf, torch::kFloat32, SN, "act_buf");
+  check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
+  check_out(cut_slot, torch::kInt32, a.steps, "cut_slot");
+  TORCH_CHECK(n_cuts >= 0 && n_cuts <= a.steps, "n_cuts out of range");
+  a.n_cuts = (int)n_cuts;
+  check_f32_gpu(cut_final, "cut_final");
+  TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
+                  cut_final.size(1) == a.N && cut_final.size(2) == 3,
+              "cut_final must be [n_cuts, N, 3]");
+  check_f32_gpu(seg_returns, "seg_returns");
+  TORCH_CHECK(seg_returns.dim() == 2 && seg_returns.size(0) == a.N &&
+                  seg_returns.size(1) >= std::max(a.n_cuts, 1),
+              "seg_returns must be [N, n_segs]");
+  a.n_segs = (int)seg_returns.size(1);
+  for (const torch::Tensor* t : {&act_buf, &rew_buf, &cut_slot, &cut_final, &seg_returns})
+    TORCH_CHECK(t->device() == obs_full.device(), "replay_scatter: mixed devices");
+  a.obs_full = obs_full.data_ptr<float>();
+  a.act_buf = act_buf.data_ptr<float>();
+  a.rew_buf = rew_buf.data_ptr<float>();
+  a.cut_final = cut_final.data_ptr<float>();
+  a.cut_slot = cut_slot.data_ptr<int>();
+  a.seg_returns = seg_returns.data_ptr<float>();
+  hipLaunchKernelGGL(replay_scatter_kernel, dim3(std::min(256, (a.N + 255) / 256)),
+                     dim3(256), 0, current_stream(), a);
+  HIP_OK(hipGetLastError());
+}
+
+// write = (write + n) % cap, size = min(size + n, cap) on the device
+void ring_advance_(torch::Tensor write_dev, torch::Tensor size_dev, int64_t n,
+                   int64_t cap) {
+  for (const torch::Tensor* s : {&write_dev, &size_dev})
+    TORCH_CHECK(s->scalar_type() == torch::kInt64 && s->is_cuda() && s->numel() == 1,
+                "ring scalars must be 1-element int64 CUDA tensors");
+  TORCH_CHECK(cap >= 1 && n >= 0 && n <= cap, "ring_advance_: n outside [0, cap]");
+  hipLaunchKernelGGL(ring_advance_kernel, dim3(1), dim3(1), 0, current_stream(),
+                     reinterpret_cast<long long*>(write_dev.data_ptr<int64_t>()),
+                     reinterpret_cast<long long*>(size_dev.data_ptr<int64_t>()),
+                     (unsigned long long)n, (unsigned long long)cap);
+  HIP_OK(hipGetLastError());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("pendulum_collect_fused", &pendulum_collect_fused,
+        "whole-epoch Pendulum replay collection in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"), py::arg("mode"),
+        py::arg("noise_scale"), py::arg("limit"), py::arg("low"), py::arg("high"),
+        py::arg("action_seed"), py::arg("env_seed"), py::arg("cuts"),
+        py::arg("start_with_reset"), py::arg("ctr"), py::arg("state"),
+        py::arg("steps"), py::arg("storage"), py::arg("write_dev"),
+        py::arg("size_dev"), py::arg("seg_returns"), py::arg("last_obs"),
+        py::arg("wide_threads"));
+  m.def("pendulum_collect_fused_lds_bytes", &pendulum_collect_fused_lds_bytes_py,
+        "dynamic LDS of pendulum_collect_fused for an actor [3, ..., 1]");
+  m.def("pendulum_collect_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH,
+                                      ROLLOUT_MAX_CUTS, (int64_t)MLP_LDS_BUDGET};
+        },
+        "(max layers, max width, max cuts, LDS budget in bytes) of "
+        "pendulum_collect_fused");
+  m.def("uniform_sample", &uniform_sample,
+        "Philox uniform actions in [low, high] (gfx950)", py::arg("out"),
+        py::arg("low"), py::arg("high"), py::arg("seed"), py::arg("offset"),
+        py::arg("offset_ctr") = py::none());
+  m.def("replay_scatter", &replay_scatter,
+        "ring write of one captured Pendulum epoch's buffers (gfx950)",
+        py::arg("obs_full"), py::arg("act_buf"), py::arg("rew_buf"),
+        py::arg("cut_final"), py::arg("cut_slot"), py::arg("n_cuts"),
+        py::arg("storage"), py::arg("write_dev"), py::arg("size_dev"),
+        py::arg("seg_returns"));
+  m.def("ring_advance_", &ring_advance_,
+        "advance the replay ring's device write position and fill (gfx950)");
   m.def("pendulum_rollout_fused", &pendulum_rollout_fused,
         "whole-epoch Pendulum rollout in one persistent kernel (gfx950)",
         py::arg("weights"), py::arg("biases"), py::arg("acts"),

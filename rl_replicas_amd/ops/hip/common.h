@@ -308,6 +308,61 @@ struct PendulumRolloutArgs {
   uint64_t policy_seed, env_seed;
 };
 
+// The replay ring as the collect kernels see it (replay_buffer.py): the five
+// storage tensors, the capacity, and the write position held on the device.
+// Kernels reduce *write modulo cap before use, so no value of the scalar
+// can index outside the storage.
+struct ReplayRing {
+  float* obs;   // [cap, 3]
+  float* act;   // [cap, 1]
+  float* rew;   // [cap]
+  float* nxt;   // [cap, 3]
+  float* dn;    // [cap]
+  const long long* write;  // device scalar: next slot to write
+  unsigned long long cap;
+};
+
+// persistent Pendulum replay collection (pendulum_collect_kernels.hip): one
+// workgroup carries ROLLOUT_ROWS instances through all `steps` iterations of
+// behaviour action -> transition / lockstep autoreset -> ring write.
+#define COLLECT_NOISED 0   // actor forward + clipped Gaussian noise
+#define COLLECT_UNIFORM 1  // uniform in [low, high]; no net is read
+// LDS row stride of the wide regime's 16-row activation tiles
+#define COLLECT_WIDE_LDSW (MLP_MAX_WIDTH + 4)
+struct PendulumCollectArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;                  // 0 in uniform mode
+  double* state;           // [N, 2] env carry (read unless start_with_reset)
+  ReplayRing ring;
+  float* seg_returns;      // [N, n_segs] per-row segment reward sums
+  float* last_obs;         // [N, 3] observation of the carry after the epoch
+  const unsigned long long* ctr;  // device RNG counter (read once)
+  int cut_step[ROLLOUT_MAX_CUTS];  // ascending
+  int n_cuts, n_segs;
+  int N, steps;
+  int start_with_reset;
+  int mode;                // COLLECT_NOISED | COLLECT_UNIFORM
+  float noise_scale, limit;  // noised mode
+  float low, high;           // uniform mode
+  uint64_t action_seed, env_seed;
+};
+
+// the multi-kernel body's ring write (offpolicy_kernels.hip): the buffers
+// of steps x (action -> pendulum_env_step) into the same slots
+struct ReplayScatterArgs {
+  const float* obs_full;   // [steps + 1, N, 3]
+  const float* act_buf;    // [steps, N, 1]
+  const float* rew_buf;    // [steps, N]
+  const float* cut_final;  // [n_cuts, N, 3]
+  const int* cut_slot;     // [steps]: index into cut_final, -1 off the cuts
+  ReplayRing ring;
+  float* seg_returns;      // [N, n_segs]
+  int N, steps, n_cuts, n_segs;
+};
+
 // replay-ring minibatch gather (offpolicy_kernels.hip / bindings.hip)
 struct ReplayGatherArgs {
   const float* obs;   // [cap, O] ring storage

@@ -17,11 +17,15 @@
 //                         clamp(scale*z, +-clip), +-limit) in one pass
 //   q_target_min2_kernel  min-twin bootstrap target
 //
-// All three read their RNG offset through an optional device counter so
+// and the collection side of a device-env epoch (replay_scatter_kernel,
+// ring_advance_kernel, at the end of this file).
+//
+// The first three read their RNG offset through an optional device counter so
 // a hipGraph replay of the whole train loop draws fresh randomness
 // (same pattern as sample_kernels.hip).
 #include "common.h"
 #include "philox.h"
+#include "rollout_steps.h"
 
 // out = clamp(a + clamp(scale * z, -clip, clip), -limit, limit)
 // (reference td3.py:325-341)
@@ -87,5 +91,58 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(
     } else {
       a.dn_out[row] = a.dn[idx];
     }
+  }
+}
+
+// Ring write of one captured Pendulum epoch (the multi-kernel body of
+// ops/fused_rollout.py::GraphedPendulumCollect): one thread per instance
+// walks its `steps` transitions in order and writes them to the slots
+// (write + row * steps + t) % cap — the slots, values and segment sums of
+// pendulum_collect_fused_f32.  Cut steps store the pre-reset successor from
+// cut_final and done = 1.
+__global__ __launch_bounds__(256) void replay_scatter_kernel(ReplayScatterArgs a) {
+  const unsigned long long cap = a.ring.cap;
+  const unsigned long long write = (unsigned long long)*a.ring.write % cap;
+  const int N = a.N, steps = a.steps;
+  for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
+    float seg_acc = 0.f;
+    int cslot = -1;
+    for (int t = 0; t < steps; ++t) {
+      cslot = a.cut_slot[t];
+      if (cslot >= a.n_cuts) cslot = -1;  // device data: never past cut_final
+      const float* const ob = a.obs_full + ((long)t * N + row) * 3;
+      const float* const nx = cslot >= 0
+                                  ? a.cut_final + ((long)cslot * N + row) * 3
+                                  : a.obs_full + ((long)(t + 1) * N + row) * 3;
+      const unsigned long long slot = ring_slot(write, cap, row, steps, t);
+      #pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        a.ring.obs[slot * 3 + k] = ob[k];
+        a.ring.nxt[slot * 3 + k] = nx[k];
+      }
+      const float rew = a.rew_buf[(long)t * N + row];
+      a.ring.act[slot] = a.act_buf[(long)t * N + row];
+      a.ring.rew[slot] = rew;
+      a.ring.dn[slot] = cslot >= 0 ? 1.f : 0.f;
+      seg_acc += rew;
+      if (cslot >= 0) {
+        a.seg_returns[(long)row * a.n_segs + cslot] = seg_acc;
+        seg_acc = 0.f;
+      }
+    }
+    // the open segment (the last step is no cut)
+    if (cslot < 0) a.seg_returns[(long)row * a.n_segs + a.n_segs - 1] = seg_acc;
+  }
+}
+
+// the ring's device scalars after n transitions were written:
+// write = (write + n) % cap, size = min(size + n, cap); one thread
+__global__ void ring_advance_kernel(long long* write, long long* size,
+                                    unsigned long long n, unsigned long long cap) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const unsigned long long w = (unsigned long long)*write % cap;
+    *write = (long long)((w + n) % cap);
+    const unsigned long long sz = *size < 0 ? 0ull : (unsigned long long)*size;
+    *size = (long long)(sz + n < cap ? sz + n : cap);
   }
 }

@@ -57,6 +57,66 @@ DEV_INLINE void mlp_fwd_tile_epilogue(f32x4 acc, const float* B, int act, int j,
   }
 }
 
+// One 16x16 output tile of a wide Linear layer (in_d up to MLP_MAX_WIDTH):
+// activations from the LDS tile xt[16][LDSW], the weight row wrow[in_d] of
+// output column j from global memory.  Lane (i = lane & 15, k = lane >> 4).
+// The accumulation order is fixed: two chains over the 8-wide K blocks, the
+// single 4-block and the ragged tail on the first chain, then acc += acc2.
+// Shared by mlp_layer_fwd_wide_f32 and pendulum_collect_fused_f32.
+template <int LDSW>
+DEV_INLINE f32x4 mlp_fwd_tile_wide(const float* xt, const float* wrow, int in_d,
+                                   int i, int k, bool jok) {
+  const int in4 = in_d & ~3;
+  const int in8 = in_d & ~7;
+  // two independent accumulator chains double the MFMA/load ILP
+  // (the K chain is otherwise a serial dependent sequence)
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < in8; k0 += 8) {
+    float bv0 = 0.f, bv1 = 0.f;
+    if (jok) {
+      // every lane of a 16-lane group reads its K element of the
+      // broadcast W chunk (4x fewer load instructions than scalar)
+      bv0 = wrow[k0 + k];
+      bv1 = wrow[k0 + 4 + k];
+    }
+    const float a0 = xt[i * LDSW + k0 + k];
+    const float a1 = xt[i * LDSW + k0 + 4 + k];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv0, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv1, acc2, 0, 0, 0);
+  }
+  for (int k0 = in8; k0 < in4; k0 += 4) {
+    float bv = jok ? wrow[k0 + k] : 0.f;
+    const float a = xt[i * LDSW + k0 + k];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+  }
+  if (in4 < in_d) {  // ragged K tail
+    const int kk = in4 + k;
+    float a = (kk < in_d) ? xt[i * LDSW + kk] : 0.f;
+    float bv = (jok && kk < in_d) ? wrow[kk] : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, acc, 0, 0, 0);
+  }
+  acc[0] += acc2[0]; acc[1] += acc2[1]; acc[2] += acc2[2]; acc[3] += acc2[3];
+  return acc;
+}
+
+// one uniform action element in [low, high], keyed by (seed, offset, i)
+DEV_INLINE float uniform_sample_elem(float low, float high, uint64_t seed,
+                                     uint64_t offset, uint32_t i) {
+  uint32_t r[4];
+  philox4(seed, offset, i, r);
+  return low + (high - low) * u32_to_open_unit(r[0]);
+}
+
+// slot of transition (row, t) of an epoch written instance-major from ring
+// position `write` (already reduced modulo cap)
+DEV_INLINE unsigned long long ring_slot(unsigned long long write,
+                                        unsigned long long cap, int row, int steps,
+                                        int t) {
+  return (write + (unsigned long long)row * (unsigned long long)steps +
+          (unsigned long long)t) % cap;
+}
+
 // one action element: mean + exp(log_std[d]) * z, z keyed by
 // (seed, offset, i); noise_scale >= 0 overrides sigma, limit >= 0 clips
 DEV_INLINE float gaussian_sample_elem(float mean, const float* log_std, int d,

@@ -40,3 +40,14 @@ __global__ __launch_bounds__(256) void categorical_sample_kernel(
     out[row] = categorical_sample_row(logits + (long)row * N, N, seed, offset,
                                       (uint32_t)row);
 }
+
+// uniform actions in [low, high] (RandomPolicy over a Box with one bound
+// pair): element i = row * A + d is keyed by (seed, offset, i)
+// (offset_ptr: optional device counter, as in gaussian_sample_kernel)
+__global__ __launch_bounds__(256) void uniform_sample_kernel(
+    float* __restrict__ out, int total, float low, float high, uint64_t seed,
+    uint64_t offset, const unsigned long long* __restrict__ offset_ptr) {
+  if (offset_ptr) offset += *offset_ptr;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256)
+    out[i] = uniform_sample_elem(low, high, seed, offset, (uint32_t)i);
+}

@@ -36,13 +36,47 @@ class ReplayBuffer:
         # device mirror of current_size, read by the fused gather kernel
         # (lets one captured hipGraph keep sampling as the ring fills)
         self._size_dev: Optional[torch.Tensor] = None
+        # device mirror of _write: where a device-side collect
+        # (samplers.DeviceReplaySampler) writes its next transition
+        self._write_dev: Optional[torch.Tensor] = None
         self._gather_offset = 0
 
     def _sync_size_dev(self) -> None:
+        """Host bookkeeping -> device mirrors (every host-side ring move)."""
         if self.device is not None and self.device.type == "cuda":
             if self._size_dev is None:
                 self._size_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+            if self._write_dev is None:
+                self._write_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
             self._size_dev.fill_(self.current_size)
+        if self._write_dev is not None:
+            self._write_dev.fill_(self._write)
+
+    # ------------------------------------------------------------------
+    def device_ring(self, obs_dim: int, act_shape):
+        """The ring as a device-side collect graph sees it: ([observations,
+        actions, rewards, next_observations, dones], write scalar, size
+        scalar).  Allocates the storage for (obs_dim, act_shape) if nothing
+        is stored yet.  The graph advances both scalars itself; the host
+        follows with `advance_host`."""
+        assert self.device is not None and self.device.type == "cuda"
+        if self._storage is None:
+            self._allocate(int(obs_dim), tuple(act_shape))
+        if self._size_dev is None or self._write_dev is None:
+            self._sync_size_dev()
+        st = self._storage
+        return (
+            [st["observations"], st["actions"], st["rewards"],
+             st["next_observations"], st["dones"]],
+            self._write_dev,
+            self._size_dev,
+        )
+
+    def advance_host(self, n: int) -> None:
+        """Host side of a device-side write of n transitions: the same
+        arithmetic the graph's ring_advance node did, no synchronisation."""
+        self._write = (self._write + n) % self.buffer_size
+        self.current_size = min(self.current_size + n, self.buffer_size)
 
     # ------------------------------------------------------------------
     def _allocate(self, obs_dim: int, act_shape) -> None:
@@ -58,6 +92,15 @@ class ReplayBuffer:
 
     def add_experience(self, experience: Experience) -> None:
         """Append all transitions of `experience` to the ring."""
+        stored_in = getattr(experience, "stored_in_buffer", None)
+        if stored_in is not None:
+            # a device-side collect already wrote these transitions
+            if stored_in is self:
+                return
+            raise ValueError(
+                "this experience's transitions were written into another "
+                "ReplayBuffer by its sampler; it carries no data to add here"
+            )
         flat = getattr(experience, "_flat_cache", None)
         if (
             flat is not None

@@ -1,0 +1,111 @@
+"""Device-resident replay collection — the off-policy twin of DeviceSampler.
+
+Pairs `envs.DevicePendulumEnv` with one `ReplayBuffer` on the same GPU.  An
+epoch of DDPG/TD3 collection (warm-up `RandomPolicy` or the noised actor) is
+ONE captured hipGraph (`ops/fused_rollout.py::GraphedPendulumCollect`) that
+steps the env and writes every transition straight into the buffer's HBM
+ring at the write position the buffer holds on the device.  Nothing is
+staged, transposed or copied a second time; the only read-back of an epoch
+is the per-episode returns for the metrics layer.
+
+The returned `Experience` carries the episode structure (`episode_returns`,
+`episode_lengths`, `dones`, as `DeviceSampler._build_experience` orders
+them), no flat cache, and `stored_in_buffer`: the buffer that already holds
+its transitions.  `ReplayBuffer.add_experience` returns at once for it, so
+`OffPolicyAlgorithm.learn` runs unchanged.
+
+Wherever the collect graph does not apply (CPU, graphs disabled, another
+policy or env, more transitions than the ring holds, a full graph cache)
+`sample()` is `DeviceSampler.sample()`: the experience then has a flat cache
+and no marker, and `add_experience` stores it the usual way.  Both routes
+move the same ring bookkeeping, so they can be mixed in any order.
+
+No reference counterpart (the reference samples one env serially on the
+host, batch_sampler.py:55-99).
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+
+from rl_replicas_amd.envs.device import DevicePendulumEnv
+from rl_replicas_amd.experience import Experience
+from rl_replicas_amd.policies import Policy
+from rl_replicas_amd.replay_buffer import ReplayBuffer
+from rl_replicas_amd.samplers.device_sampler import DeviceSampler
+
+
+class DeviceReplaySampler(DeviceSampler):
+    def __init__(self, device_env: DevicePendulumEnv, replay_buffer: ReplayBuffer,
+                 seed: Optional[int] = None):
+        super().__init__(device_env, seed=seed, is_continuous=True)
+        buffer_device = replay_buffer.device
+        if device_env.device.type == "cuda" and (
+            buffer_device is None or buffer_device.type != "cuda"
+        ):
+            raise ValueError(
+                "DeviceReplaySampler needs its ReplayBuffer on the env's device "
+                f"({device_env.device}), got {buffer_device}"
+            )
+        self.replay_buffer = replay_buffer
+
+    def sample(self, num_samples: int, policy: Policy) -> Experience:
+        from rl_replicas_amd.ops import fused_rollout
+
+        env = self.env
+        N = self.num_envs
+        buffer = self.replay_buffer
+        if (num_samples % N != 0 or num_samples > buffer.buffer_size
+                or not fused_rollout.pendulum_collect_supported(policy, env, buffer)):
+            return super().sample(num_samples, policy)
+        steps = num_samples // N
+        first = self._obs is None
+        horizon = env.spec.max_episode_steps
+        start_elapsed = 0 if first else env._elapsed
+        # lockstep truncation boundaries are pure host arithmetic
+        cuts: Tuple[int, ...] = tuple(
+            t for t in range(steps)
+            if horizon is not None and (start_elapsed + t + 1) % horizon == 0
+        )
+        mode = fused_rollout.pendulum_collect_mode(policy, env)
+        key = (steps, cuts, first, mode)
+        g = self._graphs.get(key)
+        if g is None:
+            if len(self._graphs) >= 8:  # the cache cap of DeviceSampler
+                return super().sample(num_samples, policy)
+            if first and self.seed is not None:
+                env.seed(self.seed)
+            if self._graph_ctr is None:
+                self._graph_ctr = fused_rollout.make_counter(env.device)
+            g = fused_rollout.GraphedPendulumCollect(
+                policy, env, buffer, steps, cuts, first, mode, self._graph_ctr
+            )
+            self._graphs[key] = g
+        g.replay()
+        self._obs = g.last_obs
+        env._elapsed = steps - (cuts[-1] + 1) if cuts else start_elapsed + steps
+        return self._build_marked_experience(steps, cuts, g.seg_returns)
+
+    def _build_marked_experience(self, steps: int, cuts: Tuple[int, ...],
+                                 seg_returns) -> Experience:
+        N = self.num_envs
+        bounds = []  # (length, done), as in DeviceSampler._build_experience
+        start = 0
+        for c in cuts:
+            bounds.append((c + 1 - start, True))
+            start = c + 1
+        if start < steps:
+            bounds.append((steps - start, False))
+        experience = Experience()
+        # one tiny D2H: per-episode returns for the metrics layer
+        experience.episode_returns = [
+            float(r) for r in seg_returns.cpu().numpy().reshape(-1)
+        ]
+        experience.episode_lengths = [length for length, _ in bounds] * N
+        experience.dones = [
+            np.concatenate([np.zeros(length - 1, dtype=bool), [done]])
+            for length, done in bounds
+        ] * N
+        experience.stored_in_buffer = self.replay_buffer
+        return experience

@@ -1,0 +1,740 @@
+"""Device-side replay collection on DevicePendulumEnv (gpu-marked): the
+persistent kernel pendulum_collect_fused against the captured multi-kernel
+body with torch.equal (both inline the row code of rollout_steps.h and use
+the same Philox offsets, so no tolerance applies), ring placement, the
+transition against the numpy env, the two behaviour policies, the gate, the
+bindings' argument checks, and DDPG / TD3 end to end.
+
+N = 5 (less than one 16-row tile), 16 (exactly one), 37 (two tiles and a
+5-row tail); steps = 6 with horizon 4, so the first epoch cuts after step 3
+and the carried second one after steps 1 and 5.  Nets (ReLU, Tanh head):
+[3,64,32,1] and [3,7,1] narrow; [3,256,256,1] (the benchmark actor) and
+[3,70,256,1] wide, whose K = 3 has only the ragged tail, K = 70 8-blocks,
+the 4-block and a tail, K = 256 8-blocks only."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+pytestmark = pytest.mark.gpu
+
+DEVICE = "cuda"
+NS = [5, 16, 37]
+NETS = {"bench_narrow": [3, 64, 32, 1], "awkward": [3, 7, 1],
+        "bench_wide": [3, 256, 256, 1], "ragged_wide": [3, 70, 256, 1]}
+MODES = ["noised", "uniform"]
+STEPS = 6
+HORIZON = 4
+CTR_BASE = 1 << 40
+CUTS_FROM_RESET = (3,)
+CUTS_CARRY = (1, 5)  # elapsed 2 after the first epoch
+RING = ("observations", "actions", "rewards", "next_observations", "dones")
+SENTINEL = -777.0
+
+
+def _ulp_close(got32, want64):
+    want32 = np.asarray(want64).astype(np.float32)
+    return (np.abs(got32 - want32) <= np.spacing(np.abs(want32))).all()
+
+
+def _obs_of(state64):
+    th, thdot = state64.T
+    return np.stack([np.cos(th), np.sin(th), thdot], axis=1)
+
+
+def _actor(dims):
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.policies import DeterministicPolicy
+
+    net = MLP(dims, activation_function=nn.ReLU,
+              output_activation_function=nn.Tanh).to(DEVICE)
+    return net, DeterministicPolicy(net, ops.make_adam(net.parameters(), lr=1e-3))
+
+
+class World:
+    def __init__(self, n, dims=None, cap=4096, noise=0.1, torch_seed=77, seed=5,
+                 horizon=HORIZON, sentinel=True):
+        from rl_replicas_amd.envs import DevicePendulumEnv
+        from rl_replicas_amd.policies import RandomPolicy
+        from rl_replicas_amd.replay_buffer import ReplayBuffer
+        from rl_replicas_amd.samplers import DeviceReplaySampler
+        from rl_replicas_amd.utils import add_noise_to_get_action
+
+        torch.manual_seed(torch_seed)
+        self.n = n
+        self.env = DevicePendulumEnv(n, device=DEVICE, max_episode_steps=horizon)
+        self.buf = ReplayBuffer(cap, device=DEVICE)
+        self.sampler = DeviceReplaySampler(self.env, self.buf, seed=seed)
+        self.net, det = _actor(dims or NETS["awkward"])
+        self.policies = {
+            "noised": add_noise_to_get_action(det, self.env.action_space, noise),
+            "uniform": RandomPolicy(self.env.action_space),
+        }
+        if sentinel:  # torch.empty storage may hold NaNs: whole-ring compares need values
+            storage, _, _ = self.buf.device_ring(3, (1,))
+            for t in storage:
+                t.fill_(SENTINEL)
+
+    def epoch(self, mode, steps=STEPS):
+        """One sample() + add_experience(); a snapshot of everything."""
+        before = set(self.sampler._graphs)
+        write_before = self.buf._write
+        exp = self.sampler.sample(self.n * steps, self.policies[mode])
+        self.buf.add_experience(exp)
+        torch.cuda.synchronize()
+        new = set(self.sampler._graphs) - before
+        snap = {
+            "exp": exp, "write_before": write_before, "write": self.buf._write,
+            "len": len(self.buf), "new_keys": new,
+            "state": self.env.state.clone(),
+            "ring": {k: v.clone() for k, v in self.buf._storage.items()},
+            "write_dev": int(self.buf._write_dev.item()),
+            "size_dev": int(self.buf._size_dev.item()),
+        }
+        if self.sampler._graph_ctr is not None:
+            snap["ctr"] = int(self.sampler._graph_ctr.item())
+        return snap
+
+    def graph(self, cuts, reset, mode, steps=STEPS):
+        return self.sampler._graphs[(steps, cuts, reset, mode)]
+
+
+def _two_epochs(monkeypatch, fused, n, dims, mode, **kw):
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1" if fused else "0")
+    w = World(n, dims, **kw)
+    out = []
+    for e, (cuts, reset) in enumerate(((CUTS_FROM_RESET, True), (CUTS_CARRY, False))):
+        snap = w.epoch(mode)
+        g = w.graph(cuts, reset, mode)
+        snap["g"] = g
+        snap["seg_returns"] = g.seg_returns.clone()
+        snap["last_obs"] = g.last_obs.clone()
+        out.append(snap)
+    return w, out
+
+
+def _rows(snap, n, steps=STEPS, cap=None):
+    """The epoch's transitions as [n, steps, ...] views of the ring clone."""
+    cap = cap or snap["ring"]["rewards"].shape[0]
+    idx = (snap["write_before"] + torch.arange(n * steps, device=DEVICE)) % cap
+    return {k: v[idx].view(n, steps, *v.shape[1:]) for k, v in snap["ring"].items()}
+
+
+# ---------------------------------------------------------------------------
+# 1. fused equals multi-kernel body
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("net", list(NETS))
+@pytest.mark.parametrize("n", NS)
+def test_fused_equals_multi_kernel_body(monkeypatch, n, net, mode):
+    _, f = _two_epochs(monkeypatch, True, n, NETS[net], mode)
+    _, p = _two_epochs(monkeypatch, False, n, NETS[net], mode)
+    for e, (a, b) in enumerate(zip(f, p)):
+        assert a["g"].fused and not b["g"].fused
+        assert a["g"].mode == b["g"].mode == mode
+        assert a["ctr"] == b["ctr"] == CTR_BASE + (e + 1) * (STEPS + 1)
+        for k in RING:
+            assert torch.equal(a["ring"][k], b["ring"][k]), f"{k} differs in epoch {e}"
+        for k in ("state", "seg_returns", "last_obs"):
+            assert torch.equal(a[k], b[k]), f"{k} differs in epoch {e}"
+        for k in ("write", "len", "write_dev", "size_dev"):
+            assert a[k] == b[k] == (e + 1) * n * STEPS, k
+        ea, eb = a["exp"], b["exp"]
+        assert ea.episode_returns == eb.episode_returns
+        assert ea.episode_lengths == eb.episode_lengths
+        assert all(np.array_equal(x, y) for x, y in zip(ea.dones, eb.dones))
+        assert ea.stored_in_buffer is not None and getattr(ea, "_flat_cache", None) is None
+    # the structure DeviceSampler._build_experience gives
+    assert f[0]["exp"].episode_lengths == [4, 2] * n
+    assert f[1]["exp"].episode_lengths == [2, 4] * n
+    assert [d.tolist() for d in f[0]["exp"].dones[:2]] == [[False] * 3 + [True],
+                                                           [False, False]]
+    assert f[0]["exp"].episode_returns == [
+        float(x) for x in f[0]["seg_returns"].cpu().numpy().reshape(-1)]
+    # the epochs draw fresh randomness
+    assert not torch.equal(_rows(f[0], n)["actions"], _rows(f[1], n)["actions"])
+    assert torch.isfinite(f[1]["ring"]["rewards"][: 2 * n * STEPS]).all()
+
+
+@pytest.mark.parametrize("net", ["bench_wide", "ragged_wide"])
+def test_wide_workgroup_sizes_agree(monkeypatch, net):
+    """The wide regime at 1024 threads (one column tile per wave) writes the
+    bytes it writes at 256 (four tiles per wave)."""
+    n = 37
+    monkeypatch.setenv("RL_REPLICAS_AMD_COLLECT_WG", "256")
+    _, a = _two_epochs(monkeypatch, True, n, NETS[net], "noised")
+    monkeypatch.setenv("RL_REPLICAS_AMD_COLLECT_WG", "1024")
+    _, b = _two_epochs(monkeypatch, True, n, NETS[net], "noised")
+    for x, y in zip(a, b):
+        assert x["g"].fused and y["g"].fused
+        for k in RING:
+            assert torch.equal(x["ring"][k], y["ring"][k]), k
+        for k in ("state", "seg_returns", "last_obs"):
+            assert torch.equal(x[k], y[k]), k
+
+
+# ---------------------------------------------------------------------------
+# 2. ring placement
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("cap_kind", ["exact", "wrap_mid_row", "large"])
+@pytest.mark.parametrize("n", [5, 37])
+def test_ring_placement(monkeypatch, n, cap_kind):
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    ne = n * STEPS
+    cap = {"exact": ne, "wrap_mid_row": ne * 3 // 2, "large": 4 * ne + 3}[cap_kind]
+    ref_w = World(n, cap=4096)
+    ref = [ref_w.epoch("noised"), ref_w.epoch("noised")]
+    w = World(n, cap=cap, sentinel=True)
+    got = [w.epoch("noised"), w.epoch("noised")]
+    owner = torch.full((cap,), -1, dtype=torch.int64)  # epoch that wrote the slot
+    for e in range(2):
+        assert got[e]["write_before"] == (e * ne) % cap
+        want = _rows(ref[e], n)
+        have = _rows(got[e], n, cap=cap)
+        for k in RING:  # slot of (row, t) = (write_before + row * steps + t) % cap
+            assert torch.equal(want[k], have[k]), (k, e)
+        owner[(got[e]["write_before"] + torch.arange(ne)) % cap] = e
+        assert got[e]["len"] == got[e]["size_dev"] == min((e + 1) * ne, cap)
+        assert got[e]["write"] == got[e]["write_dev"] == ((e + 1) * ne) % cap
+    assert len(w.buf) == got[1]["len"]
+    final = got[1]["ring"]
+    if cap_kind == "wrap_mid_row":
+        row, t = divmod(cap - ne, STEPS)
+        assert t != 0 and 0 < row < n  # the wrap falls inside a row
+        assert (owner == 0).sum() == cap - ne and (owner == -1).sum() == 0
+    if cap_kind == "exact":
+        assert (owner == 1).all()
+    # slots the second epoch left alone still hold the first epoch's rows ...
+    first = _rows(ref[0], n)
+    kept = torch.nonzero(owner[:ne] == 0).flatten().to(DEVICE)
+    for k in RING:
+        flat = first[k].reshape(ne, *first[k].shape[2:])
+        assert torch.equal(final[k][kept], flat[kept]), k
+    # ... and the ones nobody wrote keep the sentinel
+    untouched = torch.nonzero(owner == -1).flatten().to(DEVICE)
+    assert (cap_kind == "large") == (untouched.numel() > 0)
+    for k in RING:
+        assert (final[k][untouched] == SENTINEL).all(), k
+
+
+def test_more_transitions_than_the_ring_holds_falls_back(monkeypatch):
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    n = 5
+    cap = n * STEPS - 1
+    w = World(n, cap=cap)
+    snap = w.epoch("noised")
+    assert not w.sampler._graphs
+    exp = snap["exp"]
+    assert getattr(exp, "stored_in_buffer", None) is None
+    flat = exp.to_flat_batch()
+    assert snap["len"] == snap["size_dev"] == cap and snap["write"] == snap["write_dev"] == 0
+    for ring_key, flat_key in zip(RING, ("observations", "actions", "rewards",
+                                         "next_observations", "step_dones")):
+        assert torch.equal(snap["ring"][ring_key], flat[flat_key][-cap:]), ring_key
+
+
+# ---------------------------------------------------------------------------
+# 3. transition semantics against the host env
+# ---------------------------------------------------------------------------
+def _drive_numpy(state64, actions):
+    """PendulumEnv._step_b from state64 [n,2] with actions [n, T]; per step
+    the observation, the reward and the state."""
+    from rl_replicas_amd.envs import PendulumEnv
+
+    ref = PendulumEnv()
+    ref.state = state64.copy()
+    out = []
+    for t in range(actions.shape[1]):
+        obs, reward, _ = ref._step_b(actions[:, t : t + 1])
+        out.append((obs, reward, ref.state.copy()))
+    return out
+
+
+@pytest.mark.parametrize("net", ["bench_narrow", "bench_wide"])
+def test_transitions_match_the_host_env(monkeypatch, net):
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    n = 37
+    w = World(n, NETS[net], noise=0.5)
+    first = w.epoch("noised")
+    start = first["state"].cpu().numpy()
+    second = w.epoch("noised")
+    assert w.graph(CUTS_CARRY, False, "noised").fused
+    rows = {k: v.cpu().numpy() for k, v in _rows(second, n).items()}
+    # the carried epoch starts from the first epoch's carry
+    assert _ulp_close(rows["observations"][:, 0], _obs_of(start))
+    first_cut = CUTS_CARRY[0]
+    steps = _drive_numpy(start, rows["actions"][:, : first_cut + 1, 0])
+    for t, (obs, reward, _) in enumerate(steps):
+        assert _ulp_close(rows["rewards"][:, t], reward), t
+        # the true successor, on the cut step too
+        assert _ulp_close(rows["next_observations"][:, t], obs), t
+    # bytewise chaining off the cuts, done flags and fresh draws on them
+    for t in range(STEPS):
+        if t in CUTS_CARRY:
+            assert (rows["dones"][:, t] == 1.0).all()
+            if t + 1 < STEPS:
+                assert (np.abs(rows["observations"][:, t + 1, 2]) < 1.0).all()
+                assert not np.array_equal(rows["observations"][:, t + 1],
+                                          rows["next_observations"][:, t])
+        else:
+            assert (rows["dones"][:, t] == 0.0).all()
+            if t + 1 < STEPS:
+                assert np.array_equal(rows["next_observations"][:, t],
+                                      rows["observations"][:, t + 1])
+    # the epoch ended on a cut: the carry is a fresh draw, and last_obs is its
+    # observation
+    end = second["state"].cpu().numpy()
+    assert (np.abs(end[:, 1]) < 1.0).all() and (np.abs(end[:, 0]) < math.pi).all()
+    g = w.graph(CUTS_CARRY, False, "noised")
+    assert _ulp_close(g.last_obs.cpu().numpy(), _obs_of(end))
+
+    # the fp64 state itself, over a carried epoch without cuts
+    w2 = World(n, NETS[net], noise=0.5, horizon=100)
+    start = w2.epoch("noised")["state"].cpu().numpy()
+    snap = w2.epoch("noised")
+    rows = {k: v.cpu().numpy() for k, v in _rows(snap, n).items()}
+    steps = _drive_numpy(start, rows["actions"][:, :, 0])
+    diff = np.abs(steps[-1][2] - snap["state"].cpu().numpy()).max()
+    print(f"{net}: max abs fp64 state difference after {STEPS} steps {diff:.3e}")
+    assert diff <= 1e-12
+    for t, (obs, reward, _) in enumerate(steps):
+        assert _ulp_close(rows["rewards"][:, t], reward)
+        assert _ulp_close(rows["next_observations"][:, t], obs)
+    assert (rows["dones"] == 0.0).all()
+
+
+# ---------------------------------------------------------------------------
+# 4. actions
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "multi"])
+@pytest.mark.parametrize("net", list(NETS))
+def test_noise_zero_actions_are_the_actor_forward(monkeypatch, net, fused):
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.ops.fused_mlp import _extract_layers
+
+    n = 37
+    w, snaps = _two_epochs(monkeypatch, fused, n, NETS[net], "noised", noise=0.0)
+    weights, biases, acts = _extract_layers(w.net)
+    ext = ops._load_extension()
+    for snap in snaps:
+        assert snap["g"].fused == fused
+        rows = _rows(snap, n)
+        obs = rows["observations"].reshape(-1, 3).contiguous()
+        mean = ext.mlp_forward(obs, list(weights), list(biases), acts, False, 0)[0]
+        want = mean.clamp(-2.0, 2.0)
+        assert torch.equal(rows["actions"].reshape(-1, 1), want)
+        assert want.abs().max() > 0
+
+
+def test_noised_actions_are_clipped_to_the_limit(monkeypatch):
+    n = 37
+    _, snaps = _two_epochs(monkeypatch, True, n, NETS["bench_wide"], "noised", noise=10.0)
+    acts = torch.cat([_rows(s, n)["actions"].flatten() for s in snaps])
+    assert (acts >= -2.0).all() and (acts <= 2.0).all()
+    assert (acts == 2.0).any() and (acts == -2.0).any()
+    assert ((acts > -2.0) & (acts < 2.0)).any()
+
+
+def test_uniform_actions(monkeypatch):
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    n = 37
+    w = World(n, horizon=200)
+    draws = []
+    for e in range(10):
+        snap = w.epoch("uniform")
+        a = _rows(snap, n)["actions"].flatten()
+        assert (a > -2.0).all() and (a < 2.0).all()  # strictly inside (low, high)
+        if e < 2:  # the protocol's two epochs: no two of the N * steps draws are equal
+            assert a.unique().numel() == n * STEPS
+        draws.append(a)
+    assert len(w.sampler._graphs) == 2  # reset + carry, replayed
+    a = torch.cat(draws).double()
+    count = a.numel()
+    assert count >= 2000
+    # The further epochs are there for the mean.  Over all of them equal
+    # values are no longer impossible: an action has 2^-22 resolution on
+    # half of [-2, 2], so two distinct 32-bit Philox draws round to one
+    # fp32 with probability ~4e-8 per pair, ~0.1 expected pairs in 2220
+    # draws (the fifth epoch has one: draws 1193680398 and 1193680338).  A
+    # repeated Philox key would repeat whole rows or steps, >= 6 values.
+    repeats = count - a.unique().numel()
+    print(f"{repeats} repeated values in {count} uniform draws")
+    assert repeats <= 2
+    bound = 5 * (4 / math.sqrt(12)) / math.sqrt(count)
+    print(f"mean of {count} uniform draws {a.mean().item():.3e}, bound {bound:.3e}")
+    assert abs(a.mean().item()) <= bound
+    assert a.min() < -1.9 and a.max() > 1.9
+
+
+def test_uniform_sample_kernel_counter_and_checks():
+    from rl_replicas_amd import ops
+
+    ext = ops._load_extension()
+    a, b, c = (torch.zeros(5, 3, device=DEVICE) for _ in range(3))
+    ctr = torch.tensor([12345], dtype=torch.int64, device=DEVICE)
+    ext.uniform_sample(a, -1.0, 3.0, 99, 3, ctr)
+    ext.uniform_sample(b, -1.0, 3.0, 99, 3 + 12345)
+    ext.uniform_sample(c, -1.0, 3.0, 99, 3)
+    assert torch.equal(a, b) and not torch.equal(a, c)
+    assert (a > -1.0).all() and (a < 3.0).all() and a.unique().numel() == 15
+    with pytest.raises(RuntimeError):
+        ext.uniform_sample(torch.zeros(5, 3), -1.0, 3.0, 99, 3)
+    with pytest.raises(RuntimeError):
+        ext.uniform_sample(a, 3.0, -1.0, 99, 3)
+
+
+# ---------------------------------------------------------------------------
+# 5. episode returns
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "multi"])
+def test_episode_returns_are_the_segment_sums(monkeypatch, fused):
+    n = 37
+    _, snaps = _two_epochs(monkeypatch, fused, n, NETS["bench_narrow"], "noised")
+    for snap, cuts in zip(snaps, (CUTS_FROM_RESET, CUTS_CARRY)):
+        rew = _rows(snap, n)["rewards"].double().cpu().numpy()
+        ends = [c + 1 for c in cuts]
+        bounds = list(zip([0] + ends, ends + ([STEPS] if ends[-1] < STEPS else [])))
+        seg = snap["seg_returns"].cpu().numpy()
+        assert seg.shape == (n, len(bounds))
+        for j, (s, e) in enumerate(bounds):
+            want = rew[:, s:e].sum(axis=1)
+            tol = 2 * (e - s) * 2.0 ** -24 * np.abs(rew[:, s:e]).sum(axis=1)
+            assert (np.abs(seg[:, j] - want) <= tol).all(), (j, s, e)
+        assert snap["exp"].episode_returns == [float(x) for x in seg.reshape(-1)]
+
+
+# ---------------------------------------------------------------------------
+# 6. determinism
+# ---------------------------------------------------------------------------
+def test_identically_seeded_runs_are_bit_equal(monkeypatch):
+    n = 37
+    runs = [_two_epochs(monkeypatch, True, n, NETS["bench_wide"], "noised")[1]
+            for _ in range(2)]
+    other = _two_epochs(monkeypatch, True, n, NETS["bench_wide"], "noised", seed=6)[1]
+    for e in range(2):
+        a, b = runs[0][e], runs[1][e]
+        assert a["ctr"] == b["ctr"]
+        for k in RING:
+            assert torch.equal(a["ring"][k], b["ring"][k])
+        assert torch.equal(a["state"], b["state"])
+        assert a["exp"].episode_returns == b["exp"].episode_returns
+        assert not torch.equal(a["ring"]["observations"], other[e]["ring"]["observations"])
+
+
+def test_weights_are_read_by_pointer(monkeypatch):
+    """The net changed in place between replays of ONE graph: the next
+    epoch's actions follow it (noise 0)."""
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    n = 16
+    for net in ("bench_narrow", "bench_wide"):
+        w = World(n, NETS[net], noise=0.0, horizon=None)
+        w.epoch("noised")
+        before = w.epoch("noised")
+        with torch.no_grad():
+            for p in w.net.parameters():
+                p.zero_()
+            list(w.net.parameters())[-1].fill_(0.5)
+        after = w.epoch("noised")
+        assert len(w.sampler._graphs) == 2 and not after["new_keys"]
+        assert w.graph((), False, "noised").fused
+        a0 = _rows(before, n)["actions"]
+        a1 = _rows(after, n)["actions"]
+        assert (a0 - math.tanh(0.5)).abs().max() > 1e-3
+        assert (a1 - math.tanh(0.5)).abs().max() < 1e-6
+
+
+# ---------------------------------------------------------------------------
+# 7. gate
+# ---------------------------------------------------------------------------
+def _noised(dims, env, dtype=None):
+    from rl_replicas_amd.utils import add_noise_to_get_action
+
+    net, det = _actor(dims)
+    if dtype is not None:
+        net.to(dtype)
+    return add_noise_to_get_action(det, env.action_space, 0.1)
+
+
+def test_gate(monkeypatch):
+    """`pendulum_collect_fused_eligible` is false in each case, and sample()
+    still fills the ring: through the captured multi-kernel body where the
+    collect path applies, through DeviceSampler's eager loop and
+    add_experience where it does not.  Two cases have no route at all: no
+    code path feeds a [N,3] fp32 observation to a net whose input is not 3
+    wide or whose weights are fp64, so for them only the gate is checked."""
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.ops import fused_rollout
+    from rl_replicas_amd.policies import RandomPolicy
+
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    ext = ops._load_extension()
+    max_layers, max_width, max_cuts, max_lds = ext.pendulum_collect_fused_limits()
+    assert ext.pendulum_collect_fused_lds_bytes(NETS["bench_wide"]) <= max_lds
+    assert (ext.pendulum_collect_fused_lds_bytes([3, 64, 64, 64, 64, 1])
+            > ext.pendulum_collect_fused_lds_bytes(NETS["bench_narrow"]))
+    n = 16
+    few = (3,)
+
+    def filled(w, mode="noised", steps=STEPS, route="graph"):
+        snap = w.epoch(mode, steps)
+        assert snap["len"] == snap["size_dev"] == n * steps
+        assert torch.isfinite(snap["ring"]["rewards"][: n * steps]).all()
+        if route == "graph":
+            (g,) = w.sampler._graphs.values()
+            assert not g.fused and snap["exp"].stored_in_buffer is w.buf
+        else:
+            assert not w.sampler._graphs
+            assert getattr(snap["exp"], "stored_in_buffer", None) is None
+
+    w = World(n, NETS["bench_wide"])
+    pol, uni = w.policies["noised"], w.policies["uniform"]
+    assert fused_rollout.pendulum_collect_supported(pol, w.env, w.buf)
+    assert fused_rollout.pendulum_collect_supported(uni, w.env, w.buf)
+    assert fused_rollout.pendulum_collect_fused_eligible(pol, w.env, few)
+    assert fused_rollout.pendulum_collect_fused_eligible(uni, w.env, few)
+
+    # RL_REPLICAS_AMD_ROLLOUT_FUSED=0: the multi-kernel body
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "0")
+    assert not fused_rollout.pendulum_collect_fused_eligible(pol, w.env, few)
+    assert not fused_rollout.pendulum_collect_fused_eligible(uni, w.env, few)
+    filled(w)
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+
+    # bf16 compute: the multi-kernel body
+    monkeypatch.setenv("RL_REPLICAS_AMD_COMPUTE_DTYPE", "bf16")
+    w = World(n, NETS["bench_narrow"])
+    assert not fused_rollout.pendulum_collect_fused_eligible(w.policies["noised"], w.env, few)
+    filled(w)
+    monkeypatch.delenv("RL_REPLICAS_AMD_COMPUTE_DTYPE")
+
+    # one layer / one column too many for the kernels: DeviceSampler's loop
+    for dims in ([3] + [8] * max_layers + [1], [3, max_width + 1, 1]):
+        w = World(n, dims)
+        pol = w.policies["noised"]
+        assert not fused_rollout.pendulum_collect_fused_eligible(pol, w.env, few)
+        assert not fused_rollout.pendulum_collect_supported(pol, w.env, w.buf)
+        filled(w, route="eager")
+
+    # one cut too many for the by-value list: the multi-kernel body
+    steps = max_cuts + 1
+    w = World(n, NETS["bench_narrow"], horizon=1)
+    many = tuple(range(steps))
+    assert fused_rollout.pendulum_collect_fused_eligible(w.policies["noised"], w.env, many[:-1])
+    assert not fused_rollout.pendulum_collect_fused_eligible(w.policies["noised"], w.env, many)
+    assert not fused_rollout.pendulum_collect_fused_eligible(w.policies["uniform"], w.env, many)
+    filled(w, steps=steps)
+    assert w.graph(many, True, "noised", steps).n_segs == steps
+    assert (w.buf._storage["dones"][: n * steps] == 1.0).all()
+
+    # an input that is not 3 wide, an fp64 weight: the gate only (docstring)
+    w = World(n)
+    for pol in (_noised([4, 16, 1], w.env), _noised([3, 16, 1], w.env, torch.float64)):
+        assert not fused_rollout.pendulum_collect_fused_eligible(pol, w.env, few)
+        assert not fused_rollout.pendulum_collect_supported(pol, w.env, w.buf)
+
+    # other policies, a CPU env, graphs disabled: not the collect path
+    from rl_replicas_amd.envs import DevicePendulumEnv
+    from rl_replicas_amd.replay_buffer import ReplayBuffer
+
+    _, det = _actor([3, 16, 1])
+    assert not fused_rollout.pendulum_collect_supported(det, w.env, w.buf)
+    pol = w.policies["noised"]
+    assert not fused_rollout.pendulum_collect_supported(
+        pol, DevicePendulumEnv(n, device="cpu"), w.buf)
+    assert not fused_rollout.pendulum_collect_supported(pol, w.env, ReplayBuffer(64))
+    monkeypatch.setenv("RL_REPLICAS_AMD_DISABLE_GRAPHS", "1")
+    assert not fused_rollout.pendulum_collect_supported(pol, w.env, w.buf)
+    filled(w, route="eager")
+
+
+# ---------------------------------------------------------------------------
+# 8. binding argument checks
+# ---------------------------------------------------------------------------
+def test_bindings_check_arguments_before_launching():
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.ops.fused_mlp import _extract_layers
+
+    ext = ops._load_extension()
+    n, steps, cap = 5, 6, 64
+    net, _ = _actor(NETS["awkward"])
+    weights, biases, acts = _extract_layers(net)
+    weights, biases = list(weights), list(biases)
+
+    def fresh(cap=cap):
+        torch.manual_seed(0)
+        a = {
+            "state": torch.zeros(n, 2, dtype=torch.float64, device=DEVICE),
+            "ctr": torch.full((1,), CTR_BASE, dtype=torch.int64, device=DEVICE),
+            "storage": [torch.full((cap, 3), SENTINEL, device=DEVICE),
+                        torch.full((cap, 1), SENTINEL, device=DEVICE),
+                        torch.full((cap,), SENTINEL, device=DEVICE),
+                        torch.full((cap, 3), SENTINEL, device=DEVICE),
+                        torch.full((cap,), SENTINEL, device=DEVICE)],
+            "write_dev": torch.zeros(1, dtype=torch.int64, device=DEVICE),
+            "size_dev": torch.zeros(1, dtype=torch.int64, device=DEVICE),
+            "seg_returns": torch.zeros(n, 2, device=DEVICE),
+            "last_obs": torch.zeros(n, 3, device=DEVICE),
+        }
+        return a
+
+    def fused(a, cuts=(3,), w=weights, mode=0, steps=steps):
+        ext.pendulum_collect_fused(
+            w if mode == 0 else [], biases if mode == 0 else [],
+            acts if mode == 0 else [], mode, 0.1, 2.0, -2.0, 2.0, 11, 12,
+            list(cuts), True, a["ctr"], a["state"], steps, a["storage"],
+            a["write_dev"], a["size_dev"], a["seg_returns"], a["last_obs"], 256)
+
+    def scatter(a, obs_full=None):
+        ext.replay_scatter(
+            obs_full if obs_full is not None else torch.zeros(steps + 1, n, 3, device=DEVICE),
+            torch.zeros(steps, n, 1, device=DEVICE), torch.zeros(steps, n, device=DEVICE),
+            torch.zeros(1, n, 3, device=DEVICE),
+            torch.full((steps,), -1, dtype=torch.int32, device=DEVICE), 0,
+            a["storage"], a["write_dev"], a["size_dev"], torch.zeros(n, 1, device=DEVICE))
+
+    def untouched(a):
+        torch.cuda.synchronize()
+        return (all((t == SENTINEL).all() for t in a["storage"])
+                and (a["state"] == 0).all() and int(a["write_dev"]) == 0)
+
+    bad = []
+    a = fresh(); a["storage"][2] = a["storage"][2].double(); bad.append(a)   # dtype
+    a = fresh(); a["storage"][0] = a["storage"][0].cpu(); bad.append(a)      # device
+    a = fresh(); a["write_dev"] = a["write_dev"].cpu(); bad.append(a)        # device
+    a = fresh(); a["size_dev"] = a["size_dev"].int(); bad.append(a)          # dtype
+    a = fresh()                                                              # layout
+    a["storage"][3] = torch.full((cap, 6), SENTINEL, device=DEVICE)[:, ::2]
+    assert not a["storage"][3].is_contiguous()
+    bad.append(a)
+    a = fresh(); a["storage"][1] = a["storage"][1][: cap - 1].contiguous(); bad.append(a)
+    bad.append(fresh(cap=n * steps - 1))                                     # N*steps > cap
+    for a in bad:
+        for call in (fused, scatter):
+            with pytest.raises(RuntimeError):
+                call(a)
+        with pytest.raises(RuntimeError):
+            fused(a, mode=1)
+        assert untouched(a)
+    a = fresh()
+    for cuts in ((3, 1), (2, 2), (6,), (-1,)):  # unsorted, repeated, out of range
+        with pytest.raises(RuntimeError):
+            fused(a, cuts=cuts)
+    with pytest.raises(RuntimeError):  # the head must be 1 wide, the input 3
+        fused(a, w=[weights[0]])
+    with pytest.raises(RuntimeError):  # seg_returns sized for two segments
+        fused(a, cuts=())
+    with pytest.raises(RuntimeError):  # uniform mode takes no net
+        ext.pendulum_collect_fused(
+            weights, biases, acts, 1, 0.1, 2.0, -2.0, 2.0, 11, 12, [3], True,
+            a["ctr"], a["state"], steps, a["storage"], a["write_dev"], a["size_dev"],
+            a["seg_returns"], a["last_obs"], 256)
+    with pytest.raises(RuntimeError):  # a workgroup size the kernel is not built for
+        ext.pendulum_collect_fused(
+            weights, biases, acts, 0, 0.1, 2.0, -2.0, 2.0, 11, 12, [3], True,
+            a["ctr"], a["state"], steps, a["storage"], a["write_dev"], a["size_dev"],
+            a["seg_returns"], a["last_obs"], 512)
+    with pytest.raises(RuntimeError):
+        scatter(a, obs_full=torch.zeros(steps + 1, n, 4, device=DEVICE))
+    with pytest.raises(RuntimeError):
+        ext.ring_advance_(a["write_dev"], a["size_dev"], cap + 1, cap)
+    with pytest.raises(RuntimeError):
+        ext.ring_advance_(a["write_dev"].int(), a["size_dev"], 1, cap)
+    assert untouched(a)
+
+    # a write scalar outside the ring is reduced, never used as it stands
+    a["write_dev"].fill_(cap * 1000 + 7)
+    a["size_dev"].fill_(cap - 3)
+    fused(a)
+    ext.ring_advance_(a["write_dev"], a["size_dev"], n * steps, cap)
+    torch.cuda.synchronize()
+    assert int(a["write_dev"]) == (7 + n * steps) % cap and int(a["size_dev"]) == cap
+    written = (a["storage"][2] != SENTINEL).nonzero().flatten().cpu()
+    assert sorted(written.tolist()) == sorted((7 + np.arange(n * steps)) % cap)
+
+
+# ---------------------------------------------------------------------------
+# 9. mixing host adds and device collects
+# ---------------------------------------------------------------------------
+def test_host_adds_and_device_collects_mix(monkeypatch):
+    from rl_replicas_amd.experience import Experience
+
+    monkeypatch.setenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1")
+    n, ne, host_n = 5, 5 * STEPS, 4
+    w = World(n, cap=4096, sentinel=True)
+    first = w.epoch("uniform")
+    host = Experience(
+        observations=[[np.full(3, 100.0 + i, dtype=np.float32) for i in range(host_n)]],
+        actions=[[np.full(1, 0.5, dtype=np.float32)] * host_n],
+        rewards=[[-1.0] * host_n],
+        last_observations=[np.full(3, 200.0, dtype=np.float32)],
+        dones=[[False] * (host_n - 1) + [True]],
+        episode_returns=[-4.0], episode_lengths=[host_n],
+    )
+    w.buf.add_experience(host)
+    assert w.buf._write == ne + host_n and int(w.buf._write_dev.item()) == ne + host_n
+    second = w.epoch("uniform")
+    assert second["write_before"] == ne + host_n
+    assert second["write"] == second["write_dev"] == 2 * ne + host_n
+    assert second["len"] == second["size_dev"] == 2 * ne + host_n
+    ring = second["ring"]
+    # nothing lost: the first epoch, the host rows, the second epoch, in a row
+    for k in RING:
+        assert torch.equal(ring[k][:ne], first["ring"][k][:ne]), k
+        assert (ring[k][: 2 * ne + host_n] != SENTINEL).all(), k
+        assert (ring[k][2 * ne + host_n :] == SENTINEL).all(), k
+    assert ring["observations"][ne : ne + host_n, 0].tolist() == [100.0, 101.0, 102.0, 103.0]
+    assert ring["dones"][ne : ne + host_n].tolist() == [0.0, 0.0, 0.0, 1.0]
+    assert (ring["observations"][ne + host_n : 2 * ne + host_n].abs() <= 8.0).all()
+
+    # the fused gather draws below the new size only
+    mb = w.buf.gather_minibatch_fused(4096, seed=9, offset=0)
+    torch.cuda.synchronize()
+    assert (mb["rewards"] != SENTINEL).all() and (mb["observations"] != SENTINEL).all()
+    stored = set(ring["rewards"][: 2 * ne + host_n].tolist())
+    assert set(mb["rewards"].tolist()) <= stored
+    assert len(set(mb["rewards"].tolist())) > ne  # reaches past the first epoch
+
+
+# ---------------------------------------------------------------------------
+# 10. end to end
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("algo", ["ddpg", "td3"])
+def test_off_policy_end_to_end(tmp_path, monkeypatch, algo):
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.algorithms import DDPG, TD3
+    from rl_replicas_amd.envs import DevicePendulumEnv
+    from rl_replicas_amd.evaluator import Evaluator
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.policies import RandomPolicy
+    from rl_replicas_amd.q_function import QFunction
+    from rl_replicas_amd.replay_buffer import ReplayBuffer
+    from rl_replicas_amd.samplers import DeviceReplaySampler
+
+    monkeypatch.delenv("RL_REPLICAS_AMD_ROLLOUT_FUSED", raising=False)
+    torch.manual_seed(0)
+    env = DevicePendulumEnv(10, device=DEVICE)
+    pnet, policy = _actor([3, 32, 1])
+    qnets = [MLP([4, 32, 1], activation_function=nn.ReLU).to(DEVICE)
+             for _ in range(2 if algo == "td3" else 1)]
+    qs = [QFunction(q, ops.make_adam(q.parameters(), lr=1e-3)) for q in qnets]
+    buf = ReplayBuffer(1024, device=DEVICE)
+    sampler = DeviceReplaySampler(env, buf, seed=3)
+    cls = TD3 if algo == "td3" else DDPG
+    model = cls(policy, RandomPolicy(env.action_space), *qs, env, sampler, buf,
+                Evaluator(seed=4))
+    model.learn(num_epochs=3, batch_size=50, minibatch_size=16, num_start_steps=50,
+                num_steps_before_update=50, num_train_steps=2,
+                num_evaluation_episodes=0, output_dir=str(tmp_path))
+    torch.cuda.synchronize()
+    assert sorted(k[3] for k in sampler._graphs) == ["noised", "uniform"]
+    assert set(sampler._graphs) == {(5, (), True, "uniform"), (5, (), False, "noised")}
+    assert model.current_total_steps == 150
+    assert len(buf) == 150 and buf._write == 150
+    assert int(buf._write_dev.item()) == 150 and int(buf._size_dev.item()) == 150
+    assert env._elapsed == 15
+    assert torch.isfinite(buf._storage["rewards"][:150]).all()
+    for p in list(pnet.parameters()) + [p for q in qnets for p in q.parameters()]:
+        assert torch.isfinite(p).all()
