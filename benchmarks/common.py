@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from rl_replicas_amd import envs, ops
-from rl_replicas_amd.evaluator import Evaluator
+from rl_replicas_amd.evaluator import DeviceEvaluator, Evaluator
 from rl_replicas_amd.networks import MLP
 from rl_replicas_amd.policies import (
     CategoricalPolicy,
@@ -90,7 +90,11 @@ def build_on_policy(env_id: str, seed: int, device: Optional[str], num_envs: int
 
 
 def build_off_policy(env_id: str, seed: int, device: Optional[str], num_envs: int,
-                     twin: bool, env_mode: str = "cpu"):
+                     twin: bool, env_mode: str = "cpu", eval_mode: str = "host"):
+    """eval_mode "device": a DeviceEvaluator, which runs Pendulum-v1 /
+    CartPole-v1 evaluation episodes on the policy's device and every other
+    env as the host Evaluator does."""
+    assert eval_mode in ("host", "device"), eval_mode
     set_seed_for_libraries(seed)
     dev = pick_device(device)
     buffer = ReplayBuffer(int(1e6), device=dev if dev.startswith("cuda") else None)
@@ -115,5 +119,5 @@ def build_off_policy(env_id: str, seed: int, device: Optional[str], num_envs: in
         return QFunction(qnet, ops.make_adam(qnet.parameters(), lr=1e-3))
 
     qs = [make_q() for _ in range(2 if twin else 1)]
-    evaluator = Evaluator(seed=seed)
+    evaluator = DeviceEvaluator(seed=seed) if eval_mode == "device" else Evaluator(seed=seed)
     return env, sampler, policy, exploration, qs, buffer, evaluator

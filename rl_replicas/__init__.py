@@ -39,6 +39,7 @@ for _name in _SUBMODULES:
     globals()[_name] = _mod
 
 from rl_replicas_amd import (  # noqa: E402,F401
+    DeviceEvaluator,
     Evaluator,
     Experience,
     MetricsManager,

@@ -13,7 +13,7 @@ from rl_replicas_amd.version import __version__
 logging.getLogger(__name__).addHandler(logging.NullHandler())
 
 from rl_replicas_amd import algorithms, envs, networks, ops, optimizers, parallel, policies, samplers
-from rl_replicas_amd.evaluator import Evaluator
+from rl_replicas_amd.evaluator import DeviceEvaluator, Evaluator
 from rl_replicas_amd.experience import Experience
 from rl_replicas_amd.metrics_manager import MetricsManager
 from rl_replicas_amd.q_function import QFunction
@@ -30,6 +30,7 @@ __all__ = [
     "parallel",
     "policies",
     "samplers",
+    "DeviceEvaluator",
     "Evaluator",
     "Experience",
     "MetricsManager",

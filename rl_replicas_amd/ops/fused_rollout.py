@@ -47,6 +47,12 @@ transitions go straight into a ReplayBuffer's HBM ring at the write
 position the buffer holds on the device; the persistent kernel is
 `pendulum_collect_fused` (`pendulum_collect_fused_eligible`).
 
+`GraphedPendulumEval` / `GraphedCartPoleEval` run whole evaluation
+episodes (evaluator.DeviceEvaluator): from the init draw to each episode's
+end, returning only per-episode return, length and init state; the
+persistent kernels are `pendulum_eval_fused` / `cartpole_eval_fused`
+(`pendulum_eval_fused_eligible` / `cartpole_eval_fused_eligible`).
+
 No reference counterpart (the reference samples one env serially on
 the host, batch_sampler.py:55-99).
 """
@@ -654,3 +660,286 @@ class GraphedPendulumCollect:
     def replay(self) -> None:
         self.loop.replay()
         self.buffer.advance_host(self.env.num_envs * self.steps)
+
+
+# ---------------------------------------------------------------------------
+# Whole-episode policy evaluation on the device Pendulum / CartPole dynamics
+# (evaluator.DeviceEvaluator)
+# ---------------------------------------------------------------------------
+EVAL_DETERMINISTIC = "deterministic"
+EVAL_GAUSSIAN = "gaussian"
+_EVAL_MODE_CODE = {EVAL_DETERMINISTIC: 0, EVAL_GAUSSIAN: 1}  # common.h
+
+
+def pendulum_eval_mode(policy):
+    """How an evaluation turns `policy`'s net output into a Pendulum torque:
+    EVAL_DETERMINISTIC for a DeterministicPolicy over an MLP the fused-MLP
+    kernels take (the output itself; the env clamps), EVAL_GAUSSIAN for a
+    GaussianPolicy over one (a sample around it), or None."""
+    from rl_replicas_amd.policies import DeterministicPolicy
+
+    if isinstance(policy, DeterministicPolicy):
+        mode = EVAL_DETERMINISTIC
+    elif fop._policy_kind(policy) == "gaussian":
+        mode = EVAL_GAUSSIAN
+    else:
+        return None
+    mlp = fop._mlp_of(policy)
+    if mlp is None or _extract_layers(mlp) is None:
+        return None
+    return mode
+
+
+def eval_fused_default(kind: str) -> bool:
+    """Which body an evaluation graph of `kind` ("pendulum" | "cartpole")
+    takes when RL_REPLICAS_AMD_ROLLOUT_FUSED is unset: the persistent kernel
+    where it beat the multi-kernel body beyond the two bodies' run-to-run
+    spread at 5 episodes (profiles/bench_device_eval_1gpu.json,
+    docs/ARCHITECTURE.md)."""
+    return True
+
+
+def _eval_fused_common(policy, kind: str, ext, limits, lds_bytes, in_dim: int) -> bool:
+    import os
+
+    default = "1" if eval_fused_default(kind) else "0"
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", default) == "0":
+        return False
+    if ops.compute_bf16() != 0:
+        return False
+    weights, biases, _ = _extract_layers(fop._mlp_of(policy))
+    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
+    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
+    max_layers, max_width, max_lds = limits
+    if len(weights) > max_layers or max(dims) > max_width or dims[0] != in_dim:
+        return False
+    if any(t.dtype != torch.float32 for t in (*weights, *biases)):
+        return False
+    return lds_bytes(dims) <= max_lds
+
+
+def pendulum_eval_fused_eligible(policy) -> bool:
+    """Whether a Pendulum evaluation runs as ONE persistent kernel
+    (pendulum_eval_fused, eval_kernels.hip) instead of the multi-kernel
+    body: fp32 compute and parameters, a net [3, ..., 1] within the binding's
+    own limits, one log_std for a Gaussian policy.
+    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    mode = pendulum_eval_mode(policy)
+    if mode is None:
+        return False
+    ext = ops._load_extension()
+    weights, _, _ = _extract_layers(fop._mlp_of(policy))
+    if int(weights[-1].shape[0]) != 1:
+        return False
+    if mode == EVAL_GAUSSIAN and (policy.log_std.numel() != 1
+                                  or policy.log_std.dtype != torch.float32):
+        return False
+    return _eval_fused_common(policy, "pendulum", ext, ext.pendulum_eval_fused_limits(),
+                              ext.pendulum_eval_fused_lds_bytes, 3)
+
+
+def cartpole_eval_fused_eligible(policy) -> bool:
+    """Whether a CartPole evaluation runs as ONE persistent kernel
+    (cartpole_eval_fused, eval_kernels.hip) instead of the multi-kernel
+    body: fp32 compute and parameters, a categorical net [4, ..., n_act]
+    with every width <= 64, within the binding's own limits.
+    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    if fop._policy_kind(policy) != "categorical":
+        return False
+    mlp = fop._mlp_of(policy)
+    if mlp is None or _extract_layers(mlp) is None:
+        return False
+    ext = ops._load_extension()
+    return _eval_fused_common(policy, "cartpole", ext, ext.cartpole_eval_fused_limits(),
+                              ext.cartpole_eval_fused_lds_bytes, 4)
+
+
+class _GraphedEval:
+    """What both evaluation graphs share: the per-episode outputs, the two
+    device counters and the captured loop.
+
+    Philox contract (both bodies): the init draw at (env_seed, *reset_ctr,
+    row), the action of step t at (policy_seed, t + *ctr, row).  Every replay
+    advances `ctr` by `horizon`; `reset_ctr` advances by 1 only when
+    `advance_reset` (an unseeded evaluator: fresh init states per call).
+    The weight pointers are those of the live parameters."""
+
+    state_dim = 0
+
+    def __init__(self, num_episodes: int, horizon: int, ctr: torch.Tensor,
+                 reset_ctr: torch.Tensor, advance_reset: bool):
+        assert num_episodes >= 1 and horizon >= 1
+        dev = ctr.device
+        self.num_episodes = num_episodes
+        self.horizon = horizon
+        self.ctr = ctr
+        self.reset_ctr = reset_ctr
+        self.advance_reset = advance_reset
+        self.returns = torch.zeros(num_episodes, dtype=torch.float64, device=dev)
+        self.lengths = torch.zeros(num_episodes, dtype=torch.int32, device=dev)
+        self.init_state = torch.zeros(num_episodes, self.state_dim,
+                                      dtype=torch.float64, device=dev)
+        self.policy_seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
+
+    def _bump(self, ext) -> None:
+        ext.counter_add_(self.ctr, self.horizon)
+        if self.advance_reset:
+            ext.counter_add_(self.reset_ctr, 1)
+
+    def _capture(self, body) -> None:
+        # warm-up advances both counters; snapshot/restore so the first
+        # replay draws what an uncaptured first call would
+        self.loop = fop._CapturedLoop(body, [self.ctr, self.reset_ctr])
+
+    def replay(self) -> None:
+        self.loop.replay()
+
+
+class GraphedPendulumEval(_GraphedEval):
+    """One captured evaluation of `num_episodes` Pendulum episodes of
+    `horizon` steps.
+
+    Fused body (`pendulum_eval_fused_eligible`): pendulum_eval_fused, then
+    the counter bumps.  Multi-kernel body: pendulum_env_reset into a private
+    state tensor (copied to `init_state`), horizon x (mlp_forward ->
+    [gaussian_sample] -> pendulum_env_step), episode_reduce, the counter
+    bumps; it keeps `act_buf` [horizon, N, 1].  Both write the same bytes to
+    `returns`, `lengths` and `init_state`."""
+
+    state_dim = 2
+
+    def __init__(self, policy, num_episodes: int, horizon: int, env_seed: int,
+                 ctr: torch.Tensor, reset_ctr: torch.Tensor,
+                 advance_reset: bool = False):
+        super().__init__(num_episodes, horizon, ctr, reset_ctr, advance_reset)
+        ext = ops._load_extension()
+        N, dev = num_episodes, ctr.device
+        self.mode = pendulum_eval_mode(policy)
+        assert self.mode is not None
+        weights, biases, acts = _extract_layers(fop._mlp_of(policy))
+        weights, biases = list(weights), list(biases)
+        gaussian = self.mode == EVAL_GAUSSIAN
+        log_std = policy.log_std if gaussian else None
+        policy_seed = self.policy_seed
+        compute_bf16 = ops.compute_bf16()
+
+        self.fused = pendulum_eval_fused_eligible(policy)
+        wide_threads = collect_wide_threads()
+
+        if self.fused:
+            def body():
+                ext.pendulum_eval_fused(
+                    weights, biases, acts, _EVAL_MODE_CODE[self.mode],
+                    log_std.data if gaussian else None, policy_seed, env_seed,
+                    horizon, self.ctr, self.reset_ctr, self.returns, self.lengths,
+                    self.init_state, wide_threads,
+                )
+                self._bump(ext)
+        else:
+            self.state = torch.zeros(N, 2, dtype=torch.float64, device=dev)
+            self.obs_full = torch.zeros(horizon + 1, N, 3, device=dev)
+            self.rew_buf = torch.zeros(horizon, N, device=dev)
+            if gaussian:
+                self._act_buf = torch.zeros(horizon, N, 1, device=dev)
+            # the step kernel's successor rows: unused, but the graph writes
+            # them on every replay, so the storage lives as long as the graph
+            self._fin_scratch = fin_scratch = torch.zeros(N, 3, device=dev)
+            self._means: List[torch.Tensor] = []
+
+            def body():
+                means = []
+                ext.pendulum_env_reset(self.state, env_seed, 0, self.reset_ctr,
+                                       self.obs_full[0], True)
+                self.init_state.copy_(self.state)
+                for t in range(horizon):
+                    action = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                             acts, False, compute_bf16)[0]
+                    if gaussian:
+                        ext.gaussian_sample(action, log_std.data, policy_seed, t,
+                                            -1.0, -1.0, self.ctr, self._act_buf[t])
+                        action = self._act_buf[t]
+                    else:
+                        means.append(action)  # the deterministic action itself
+                    ext.pendulum_env_step(self.state, action, False, env_seed, t,
+                                          self.ctr, self.obs_full[t + 1],
+                                          fin_scratch, self.rew_buf[t])
+                ext.episode_reduce(self.rew_buf, None, self.returns, self.lengths)
+                self._bump(ext)
+                self._means = means  # the captured run's outputs
+
+        self._capture(body)
+
+    @property
+    def act_buf(self) -> torch.Tensor:
+        """[horizon, N, 1] actions of the last replay (multi-kernel body)."""
+        if self.mode == EVAL_GAUSSIAN:
+            return self._act_buf
+        return torch.stack(self._means).reshape(self.horizon, self.num_episodes, 1)
+
+
+class GraphedCartPoleEval(_GraphedEval):
+    """One captured evaluation of `num_episodes` CartPole episodes of at most
+    `horizon` steps under a CategoricalPolicy.
+
+    Fused body (`cartpole_eval_fused_eligible`): cartpole_eval_fused, which
+    stops stepping once every row of a workgroup has finished, then the
+    counter bumps.  Multi-kernel body: cartpole_env_reset into private carry
+    tensors (state copied to `init_state`), horizon x (mlp_forward ->
+    categorical_sample -> cartpole_env_step with autoreset), episode_reduce
+    over each row's first episode, the counter bumps; it keeps `act_buf`
+    [horizon, N].  Both write the same bytes to `returns`, `lengths` and
+    `init_state`."""
+
+    state_dim = 4
+
+    def __init__(self, policy, num_episodes: int, horizon: int, env_seed: int,
+                 ctr: torch.Tensor, reset_ctr: torch.Tensor,
+                 advance_reset: bool = False):
+        super().__init__(num_episodes, horizon, ctr, reset_ctr, advance_reset)
+        ext = ops._load_extension()
+        N, dev = num_episodes, ctr.device
+        assert fop._policy_kind(policy) == "categorical"
+        weights, biases, acts = _extract_layers(fop._mlp_of(policy))
+        weights, biases = list(weights), list(biases)
+        policy_seed = self.policy_seed
+        compute_bf16 = ops.compute_bf16()
+
+        self.fused = cartpole_eval_fused_eligible(policy)
+
+        if self.fused:
+            def body():
+                ext.cartpole_eval_fused(
+                    weights, biases, acts, policy_seed, env_seed, horizon,
+                    self.ctr, self.reset_ctr, self.returns, self.lengths,
+                    self.init_state,
+                )
+                self._bump(ext)
+        else:
+            self.state = torch.zeros(N, 4, dtype=torch.float64, device=dev)
+            self.elapsed = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.obs_full = torch.zeros(horizon + 1, N, 4, device=dev)
+            self.act_buf = torch.zeros(horizon, N, dtype=torch.int64, device=dev)
+            self.rew_buf = torch.zeros(horizon, N, device=dev)
+            self.done_buf = torch.zeros(horizon, N, dtype=torch.uint8, device=dev)
+            # unused successor rows the graph writes on every replay
+            self._fin_scratch = fin_scratch = torch.zeros(N, 4, device=dev)
+
+            def body():
+                ext.cartpole_env_reset(self.state, self.elapsed, env_seed, 0,
+                                       self.reset_ctr, self.obs_full[0])
+                self.init_state.copy_(self.state)
+                for t in range(horizon):
+                    logits = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                             acts, False, compute_bf16)[0]
+                    ext.categorical_sample(logits, policy_seed, t, self.ctr,
+                                           self.act_buf[t])
+                    ext.cartpole_env_step(
+                        self.state, self.elapsed, self.act_buf[t], horizon,
+                        env_seed, t, self.ctr, self.obs_full[t + 1], fin_scratch,
+                        self.rew_buf[t], self.done_buf[t],
+                    )
+                ext.episode_reduce(self.rew_buf, self.done_buf, self.returns,
+                                   self.lengths)
+                self._bump(ext)
+
+        self._capture(body)

@@ -112,6 +112,14 @@ bool pendulum_collect_fused_is_wide(const int* dims, int n_layers);
 size_t pendulum_collect_fused_lds_bytes(const int* dims, int n_layers);
 void launch_pendulum_collect_fused(const PendulumCollectArgs& a, int wide_threads,
                                    hipStream_t stream);
+bool eval_fused_is_wide(const int* dims, int n_layers);
+size_t eval_fused_lds_bytes(const int* dims, int n_layers);
+void launch_pendulum_eval_fused(const PendulumEvalArgs& a, int wide_threads,
+                                hipStream_t stream);
+void launch_cartpole_eval_fused(const CartPoleEvalArgs& a, hipStream_t stream);
+__global__ void episode_reduce_kernel(const float* rew_buf,
+                                      const unsigned char* done_buf, double* returns,
+                                      int* lengths, int N, int steps);
 __global__ void uniform_sample_kernel(float* out, int total, float low, float high,
                                       uint64_t seed, uint64_t offset,
                                       const unsigned long long* offset_ptr);
@@ -2074,6 +2082,172 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
   HIP_OK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// GPU-resident policy evaluation (eval_kernels.hip)
+// ---------------------------------------------------------------------------
+// LDS budget of the persistent evaluation kernels: the default per-workgroup
+// dynamic LDS limit, like the CartPole and Pendulum rollout kernels
+#define EVAL_FUSED_MAX_LDS (64 * 1024)
+
+// the per-episode outputs of an evaluation: returns fp64 [N], lengths int32
+// [N], init_state fp64 [N, state_dim], all contiguous on one GPU.  -> N
+static int check_eval_outputs(const torch::Tensor& returns,
+                              const torch::Tensor& lengths,
+                              const torch::Tensor& init_state, int state_dim) {
+  TORCH_CHECK(returns.is_cuda() && returns.is_contiguous() &&
+                  returns.scalar_type() == torch::kFloat64 && returns.dim() == 1 &&
+                  returns.size(0) >= 1,
+              "returns must be a contiguous float64 CUDA tensor [N]");
+  const int64_t N = returns.size(0);
+  TORCH_CHECK(N < (1LL << 24), "too many episodes");
+  TORCH_CHECK(lengths.is_cuda() && lengths.is_contiguous() &&
+                  lengths.scalar_type() == torch::kInt32 && lengths.dim() == 1 &&
+                  lengths.size(0) == N,
+              "lengths must be a contiguous int32 CUDA tensor [N]");
+  TORCH_CHECK(init_state.is_cuda() && init_state.is_contiguous() &&
+                  init_state.scalar_type() == torch::kFloat64 &&
+                  init_state.dim() == 2 && init_state.size(0) == N &&
+                  init_state.size(1) == state_dim,
+              "init_state must be a contiguous float64 CUDA tensor [N, ", state_dim, "]");
+  TORCH_CHECK(lengths.device() == returns.device() &&
+                  init_state.device() == returns.device(),
+              "returns / lengths / init_state are on different devices");
+  return (int)N;
+}
+
+// the two device counters of an evaluation, on the outputs' device
+static void check_eval_counters(const torch::Tensor& ctr, const torch::Tensor& reset_ctr,
+                                const torch::Device& dev) {
+  for (const torch::Tensor* c : {&ctr, &reset_ctr})
+    TORCH_CHECK(c->scalar_type() == torch::kInt64 && c->is_cuda() && c->numel() == 1 &&
+                    c->device() == dev,
+                "ctr / reset_ctr must be 1-element int64 tensors on the outputs' device");
+}
+
+static void check_net_device(const std::vector<torch::Tensor>& weights,
+                             const std::vector<torch::Tensor>& biases,
+                             const torch::Device& dev) {
+  for (const auto& t : weights)
+    TORCH_CHECK(t.device() == dev, "the net is on another device");
+  for (const auto& t : biases)
+    TORCH_CHECK(t.device() == dev, "the net is on another device");
+}
+
+// dims = [3, hidden..., 1] of the policy net
+int64_t pendulum_eval_fused_lds_bytes_py(std::vector<int64_t> dims) {
+  const NetLayout n = net_layout(dims, MLP_MAX_WIDTH);
+  return (int64_t)eval_fused_lds_bytes(n.dims, n.L);
+}
+
+// dims = [4, hidden..., n_act] of the policy net
+int64_t cartpole_eval_fused_lds_bytes_py(std::vector<int64_t> dims) {
+  const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
+  return (int64_t)eval_fused_lds_bytes(n.dims, n.L);
+}
+
+// N whole Pendulum episodes of `horizon` steps in one launch
+// (eval_kernels.hip): writes returns, lengths and init_state; reads both
+// counters, never advances them (counter_add_ follows).  mode
+// EVAL_DETERMINISTIC takes no log_std.  wide_threads: workgroup size of the
+// wide regime, 256 or 1024.
+void pendulum_eval_fused(std::vector<torch::Tensor> weights,
+                         std::vector<torch::Tensor> biases,
+                         std::vector<int64_t> acts, int64_t mode,
+                         c10::optional<torch::Tensor> log_std, int64_t policy_seed,
+                         int64_t env_seed, int64_t horizon, torch::Tensor ctr,
+                         torch::Tensor reset_ctr, torch::Tensor returns,
+                         torch::Tensor lengths, torch::Tensor init_state,
+                         int64_t wide_threads) {
+  PendulumEvalArgs a{};
+  a.N = check_eval_outputs(returns, lengths, init_state, 2);
+  check_eval_counters(ctr, reset_ctr, returns.device());
+  TORCH_CHECK(horizon >= 1 && horizon <= (1 << 24), "horizon out of range");
+  a.horizon = (int)horizon;
+  TORCH_CHECK(mode == EVAL_DETERMINISTIC || mode == EVAL_GAUSSIAN, "unknown mode");
+  a.mode = (int)mode;
+  const NetLayout net = net_layout(3, weights, biases, acts, MLP_MAX_WIDTH);
+  TORCH_CHECK(net.dims[net.L] == 1, "pendulum_eval_fused: the policy head must be 1 wide");
+  check_net_device(weights, biases, returns.device());
+  if (mode == EVAL_GAUSSIAN) {
+    TORCH_CHECK(log_std.has_value(), "pendulum_eval_fused: Gaussian mode needs log_std");
+    check_f32_gpu(*log_std, "log_std");
+    TORCH_CHECK(log_std->numel() == 1 && log_std->device() == returns.device(),
+                "pendulum_eval_fused: log_std must have 1 element on the outputs' device");
+    a.log_std = log_std->data_ptr<float>();
+  }
+  fill_net(a, net, weights, biases, acts);
+  TORCH_CHECK(eval_fused_lds_bytes(a.dims, a.n_layers) <= EVAL_FUSED_MAX_LDS,
+              "pendulum_eval_fused: net image exceeds the LDS budget");
+  TORCH_CHECK(wide_threads == 256 || wide_threads == 1024,
+              "pendulum_eval_fused: wide_threads must be 256 or 1024");
+  a.returns = returns.data_ptr<double>();
+  a.lengths = lengths.data_ptr<int>();
+  a.init_state = init_state.data_ptr<double>();
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.reset_ctr = ctr_ptr(c10::optional<torch::Tensor>(reset_ctr));
+  a.policy_seed = (uint64_t)policy_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_pendulum_eval_fused(a, (int)wide_threads, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
+// N whole CartPole episodes of at most `horizon` steps in one launch
+// (eval_kernels.hip): writes returns, lengths and init_state; reads both
+// counters, never advances them (counter_add_ follows).  Narrow nets only.
+void cartpole_eval_fused(std::vector<torch::Tensor> weights,
+                         std::vector<torch::Tensor> biases,
+                         std::vector<int64_t> acts, int64_t policy_seed,
+                         int64_t env_seed, int64_t horizon, torch::Tensor ctr,
+                         torch::Tensor reset_ctr, torch::Tensor returns,
+                         torch::Tensor lengths, torch::Tensor init_state) {
+  CartPoleEvalArgs a{};
+  a.N = check_eval_outputs(returns, lengths, init_state, 4);
+  check_eval_counters(ctr, reset_ctr, returns.device());
+  TORCH_CHECK(horizon >= 1 && horizon <= (1 << 24), "horizon out of range");
+  a.horizon = (int)horizon;
+  const NetLayout net = net_layout(4, weights, biases, acts, ROLLOUT_MAX_WIDTH);
+  check_net_device(weights, biases, returns.device());
+  fill_net(a, net, weights, biases, acts);
+  TORCH_CHECK(eval_fused_lds_bytes(a.dims, a.n_layers) <= EVAL_FUSED_MAX_LDS,
+              "cartpole_eval_fused: net image exceeds the LDS budget");
+  a.returns = returns.data_ptr<double>();
+  a.lengths = lengths.data_ptr<int>();
+  a.init_state = init_state.data_ptr<double>();
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.reset_ctr = ctr_ptr(c10::optional<torch::Tensor>(reset_ctr));
+  a.policy_seed = (uint64_t)policy_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_cartpole_eval_fused(a, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
+// first-episode return (fp64) and length (int32) of each row of rew_buf
+// [steps, N]: up to and including the first step done_buf [steps, N] (uint8)
+// marks, or all steps without one
+void episode_reduce(torch::Tensor rew_buf, c10::optional<torch::Tensor> done_buf,
+                    torch::Tensor returns, torch::Tensor lengths) {
+  check_f32_gpu(rew_buf, "rew_buf");
+  TORCH_CHECK(rew_buf.dim() == 2 && rew_buf.size(0) >= 1 && rew_buf.size(1) >= 1 &&
+                  rew_buf.size(0) <= (1 << 24) && rew_buf.size(1) < (1 << 24),
+              "rew_buf must be [steps, N]");
+  const int steps = (int)rew_buf.size(0);
+  const int N = (int)rew_buf.size(1);
+  const unsigned char* dn = nullptr;
+  if (done_buf.has_value()) {
+    check_out(*done_buf, torch::kUInt8, (int64_t)steps * N, "done_buf");
+    TORCH_CHECK(done_buf->device() == rew_buf.device(), "episode_reduce: mixed devices");
+    dn = done_buf->data_ptr<uint8_t>();
+  }
+  check_out(returns, torch::kFloat64, N, "returns");
+  check_out(lengths, torch::kInt32, N, "lengths");
+  TORCH_CHECK(returns.device() == rew_buf.device() && lengths.device() == rew_buf.device(),
+              "episode_reduce: mixed devices");
+  hipLaunchKernelGGL(episode_reduce_kernel, dim3(std::min(256, (N + 255) / 256)),
+                     dim3(256), 0, current_stream(), rew_buf.data_ptr<float>(), dn,
+                     returns.data_ptr<double>(), lengths.data_ptr<int>(), N, steps);
+  HIP_OK(hipGetLastError());
+}
+
 // out[i] = low + (high - low) * u, u in (0, 1] keyed by (seed, offset, i)
 void uniform_sample(torch::Tensor out, double low, double high, int64_t seed,
                     int64_t offset, c10::optional<torch::Tensor> offset_ctr) {
@@ -2149,6 +2323,38 @@ void ring_advance_(torch::Tensor write_dev, torch::Tensor size_dev, int64_t n,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("pendulum_eval_fused", &pendulum_eval_fused,
+        "N whole Pendulum episodes in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"), py::arg("mode"),
+        py::arg("log_std"), py::arg("policy_seed"), py::arg("env_seed"),
+        py::arg("horizon"), py::arg("ctr"), py::arg("reset_ctr"),
+        py::arg("returns"), py::arg("lengths"), py::arg("init_state"),
+        py::arg("wide_threads"));
+  m.def("pendulum_eval_fused_lds_bytes", &pendulum_eval_fused_lds_bytes_py,
+        "dynamic LDS of pendulum_eval_fused for a net [3, ..., 1]");
+  m.def("pendulum_eval_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH, EVAL_FUSED_MAX_LDS};
+        },
+        "(max layers, max width, LDS budget in bytes) of pendulum_eval_fused");
+  m.def("cartpole_eval_fused", &cartpole_eval_fused,
+        "N whole CartPole episodes in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"),
+        py::arg("policy_seed"), py::arg("env_seed"), py::arg("horizon"),
+        py::arg("ctr"), py::arg("reset_ctr"), py::arg("returns"),
+        py::arg("lengths"), py::arg("init_state"));
+  m.def("cartpole_eval_fused_lds_bytes", &cartpole_eval_fused_lds_bytes_py,
+        "dynamic LDS of cartpole_eval_fused for a net [4, ..., n_act]");
+  m.def("cartpole_eval_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
+                                      EVAL_FUSED_MAX_LDS};
+        },
+        "(max layers, max width, LDS budget in bytes) of cartpole_eval_fused");
+  m.def("episode_reduce", &episode_reduce,
+        "first-episode return and length of each row of a reward buffer (gfx950)",
+        py::arg("rew_buf"), py::arg("done_buf"), py::arg("returns"),
+        py::arg("lengths"));
   m.def("pendulum_collect_fused", &pendulum_collect_fused,
         "whole-epoch Pendulum replay collection in one persistent kernel (gfx950)",
         py::arg("weights"), py::arg("biases"), py::arg("acts"), py::arg("mode"),

@@ -350,6 +350,43 @@ struct PendulumCollectArgs {
   uint64_t action_seed, env_seed;
 };
 
+// persistent policy evaluation (eval_kernels.hip): one workgroup carries
+// ROLLOUT_ROWS episodes from their init draw to their end and writes only
+// the per-episode return, length and init state.
+#define EVAL_DETERMINISTIC 0  // action = the net's output (DeterministicPolicy)
+#define EVAL_GAUSSIAN 1       // action = mean + exp(log_std) * z
+struct PendulumEvalArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;
+  const float* log_std;    // [1]; Gaussian mode only
+  double* returns;         // [N] fp32 step rewards summed in step order
+  int* lengths;            // [N] == horizon
+  double* init_state;      // [N, 2]
+  const unsigned long long* ctr;        // action-stream counter (read once)
+  const unsigned long long* reset_ctr;  // init-draw counter (read once)
+  int N, horizon;
+  int mode;                // EVAL_DETERMINISTIC | EVAL_GAUSSIAN
+  uint64_t policy_seed, env_seed;
+};
+
+struct CartPoleEvalArgs {
+  const float* w[MLP_MAX_LAYERS];
+  const float* b[MLP_MAX_LAYERS];
+  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 4 (obs), dims[L] == n_act
+  int acts[MLP_MAX_LAYERS];
+  int n_layers;
+  double* returns;         // [N] == length (reward 1 per step)
+  int* lengths;            // [N] in [1, horizon]
+  double* init_state;      // [N, 4]
+  const unsigned long long* ctr;        // action-stream counter (read once)
+  const unsigned long long* reset_ctr;  // init-draw counter (read once)
+  int N, horizon;
+  uint64_t policy_seed, env_seed;
+};
+
 // the multi-kernel body's ring write (offpolicy_kernels.hip): the buffers
 // of steps x (action -> pendulum_env_step) into the same slots
 struct ReplayScatterArgs {
