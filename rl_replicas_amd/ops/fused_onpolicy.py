@@ -34,6 +34,7 @@ are not MLP-backed Gaussian/Categorical or are not on GPU.
 """
 from __future__ import annotations
 
+import gc
 import logging
 import math
 import os
@@ -295,9 +296,20 @@ def _policy_iter_binding(ext, policy, kind: str, twin: bool):
 class _CapturedLoop:
     """Capture `body()` into a hipGraph with state snapshot/restore
     around the warmup runs (warmup executes real kernels; capture does
-    not execute)."""
+    not execute).
+
+    The loop owns what it captured: it keeps `body`, so a body may use any
+    tensor it closes over, and that tensor lives exactly as long as the
+    graph that reads or writes its address.
+
+    A body usually closes over the object that holds this loop, so the two
+    form a reference cycle and a dropped graph waits for the cyclic
+    collector.  Destroying a graph while a stream captures aborts the
+    process, and torch no longer collects before a capture, so the collector
+    is held off for the length of ours."""
 
     def __init__(self, body, state_tensors: List[Tensor]):
+        self.body = body
         snapshot = [t.detach().clone() for t in state_tensors]
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
@@ -309,8 +321,14 @@ class _CapturedLoop:
             for t, snap in zip(state_tensors, snapshot):
                 t.copy_(snap)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.outputs = body()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.outputs = body()
+        finally:
+            if collecting:
+                gc.enable()
 
     def replay(self):
         self.graph.replay()

@@ -1,63 +1,52 @@
-"""hipGraph-captured device rollout (DeviceSampler fast path).
+"""hipGraph-captured device rollouts, replay collection and evaluation.
 
-The eager device rollout issues 3 kernels per env step (fused MLP
-forward, Philox action sample, fused env transition) — at 20 steps per
-epoch that is ~60 host launches of ~3.5 us each.  Here the WHOLE epoch
-rollout (optional lockstep reset / state carry, then steps x
-[forward -> sample -> env step], then one RNG-counter bump) is captured
-once and replayed as a single hipGraph per epoch.
+One construction, six classes.  The eager device loops issue 3 kernels per
+env step (fused MLP forward, Philox action sample, fused env transition);
+here a whole epoch (reset or state carry, steps x [forward -> sample -> env
+step], the trailing nodes, one RNG-counter bump) is captured once and
+replayed as a single hipGraph.  Where `_fused_gate` admits the net (fp32,
+within the binding's own limits; RL_REPLICAS_AMD_ROLLOUT_FUSED=0 declines)
+the steps of that graph are ONE persistent kernel that carries 16 env rows
+per workgroup through every step with weights and state in LDS, using the
+device functions, Philox offsets and element indices of the step kernels, so
+both bodies write the same bytes.  The multi-kernel bodies share one step
+loop per env (`_pendulum_epoch`, `_cartpole_epoch`).
 
-For the flagship shape (fp32, widths and obs dim <= 64) the 3 x steps
-kernels of that graph are ONE persistent kernel (`ppo_rollout_fused`):
-each workgroup carries 16 env rows through every step with weights and
-state in LDS, using the same device functions, Philox offsets and
-element indices as the three kernels, so the buffers hold the same bytes
-(`fused_kernel_eligible`; RL_REPLICAS_AMD_ROLLOUT_FUSED=0 keeps the
-three-kernel body).
+Randomness across replays: by-value Philox offsets are frozen at capture, so
+every RNG kernel adds a device-resident int64 counter to its offset, and the
+graph's last node advances the counter past every offset used: each replay
+draws a fresh, deterministic slice of the stream (same seed =>
+bitwise-identical run).  Weights and log_std are read by pointer, so the
+updates between epochs are visible to the next replay without re-capture.
+Lockstep envs re-capture only when the epoch's truncation pattern (`cuts`)
+changes; the samplers cap that cache.
 
-Randomness across replays: by-value Philox offsets are frozen at
-capture, so every RNG kernel adds a device-resident int64 counter
-(`offset_ctr`) to its offset; the graph's last node advances the
-counter past every offset used, so each replay draws a fresh,
-deterministic slice of the stream (same seed => bitwise-identical run,
-tests/test_gpu_train.py::test_graphed_rollout_determinism).
+What differs per class:
 
-Weights/log_std are read by pointer, so the Adam updates between
-epochs are visible to the next replay without re-capture.  Re-capture
-happens only when the epoch's lockstep-truncation pattern changes
-(bounded: the horizon/steps arithmetic cycles through at most two
-patterns when horizon % steps == 0, the benchmark shape).
-
-`GraphedCartPoleRollout` is the same construction for a
-CategoricalPolicy on `DeviceCartPoleEnv` (DeviceEpisodicSampler fast
-path): termination, truncation and autoreset are decided in-kernel per
-instance, so there are no cut patterns, and the persistent kernel is
-`cartpole_rollout_fused` (`cartpole_fused_eligible`).
-
-`GraphedPendulumRollout` is the construction for a GaussianPolicy on
-`DevicePendulumEnv` (DeviceSampler): lockstep like the synthetic envs, so
-graphs are keyed by the cut pattern, but the carry is the env's own fp64
-`state` as with CartPole; the persistent kernel is
-`pendulum_rollout_fused` (`pendulum_fused_eligible`).
-
-`GraphedPendulumCollect` is the off-policy construction on
-`DevicePendulumEnv` (DeviceReplaySampler): the behaviour policy is the
-noised deterministic actor or the uniform warm-up draw, and the epoch's
-transitions go straight into a ReplayBuffer's HBM ring at the write
-position the buffer holds on the device; the persistent kernel is
-`pendulum_collect_fused` (`pendulum_collect_fused_eligible`).
-
-`GraphedPendulumEval` / `GraphedCartPoleEval` run whole evaluation
-episodes (evaluator.DeviceEvaluator): from the init draw to each episode's
-end, returning only per-episode return, length and init state; the
-persistent kernels are `pendulum_eval_fused` / `cartpole_eval_fused`
-(`pendulum_eval_fused_eligible` / `cartpole_eval_fused_eligible`).
+  GraphedRollout          GaussianPolicy on the synthetic DeviceVectorEnv
+                          (DeviceSampler); carry in obs_full[steps];
+                          `ppo_rollout_fused`.
+  GraphedCartPoleRollout  CategoricalPolicy on DeviceCartPoleEnv
+                          (DeviceEpisodicSampler); termination, truncation
+                          and autoreset in-kernel per instance, so no cuts;
+                          `cartpole_rollout_fused`.
+  GraphedPendulumRollout  GaussianPolicy on DevicePendulumEnv (DeviceSampler);
+                          lockstep cuts, carry in the env's fp64 `state`;
+                          `pendulum_rollout_fused`.
+  GraphedPendulumCollect  noised actor or uniform warm-up draw on
+                          DevicePendulumEnv (DeviceReplaySampler), written
+                          straight into a ReplayBuffer's HBM ring;
+                          `pendulum_collect_fused`.
+  GraphedPendulumEval /   whole evaluation episodes (DeviceEvaluator), only
+  GraphedCartPoleEval     per-episode return, length and init state come
+                          back; `pendulum_eval_fused` / `cartpole_eval_fused`.
 
 No reference counterpart (the reference samples one env serially on
 the host, batch_sampler.py:55-99).
 """
 from __future__ import annotations
 
+import os
 from typing import List, Tuple
 
 import torch
@@ -67,50 +56,133 @@ from rl_replicas_amd.ops import fused_onpolicy as fop
 from rl_replicas_amd.ops.fused_mlp import _extract_layers
 
 
-def supported(policy, env) -> bool:
-    from rl_replicas_amd.envs.device import DeviceVectorEnv
+# ---------------------------------------------------------------------------
+# Gates
+# ---------------------------------------------------------------------------
+def _env_ready(env, env_cls) -> bool:
+    return (isinstance(env, env_cls) and env.device.type == "cuda"
+            and ops.hip_available() and fop._graphs_common(None))
 
-    if not (env.device.type == "cuda" and ops.hip_available()
-            and isinstance(env, DeviceVectorEnv)  # synthetic-dynamics kernels
-            and fop._graphs_common(None)
-            and fop._policy_kind(policy) == "gaussian"):
+
+def _graph_supported(policy, env, env_cls, kind: str) -> bool:
+    """A policy of `kind` over an MLP the fused-MLP kernels take, on a GPU
+    env of `env_cls`, with the extension present and graphs enabled."""
+    if not (_env_ready(env, env_cls) and fop._policy_kind(policy) == kind):
         return False
     mlp = fop._mlp_of(policy)
     return mlp is not None and _extract_layers(mlp) is not None
 
 
-def fused_kernel_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
-    """Whether the epoch runs as ONE persistent kernel (ppo_rollout_fused,
-    rollout_fused_kernels.hip) instead of steps x 3 kernels: fp32 compute,
-    a Gaussian policy without action clipping (the only kind `supported`
-    admits), every width and the obs dim <= 64, and the net + env image
-    within the kernel's LDS budget.  RL_REPLICAS_AMD_ROLLOUT_FUSED=0
-    selects the three-kernel body."""
-    import os
+def _fused_gate(weights, extra_fp32, limits, lds_bytes, in_dim: int,
+                out_dim=None, cuts=None, default: bool = True) -> bool:
+    """Whether a graph's steps run as ONE persistent kernel: not declined by
+    RL_REPLICAS_AMD_ROLLOUT_FUSED (`default` when unset), fp32 compute, and
+    the net within `limits`, the binding's own (common.h), so gate and
+    TORCH_CHECKs agree: (max_layers, max_width, [max_cuts,] max_lds).
 
-    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
+    `weights` is the net [in_dim, ..., out_dim] (None: the body reads no
+    net), `extra_fp32` what must be fp32 beside the weights, `lds_bytes`
+    maps dims to the kernel's LDS need, `cuts` is checked against max_cuts
+    where the limits carry one."""
+    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1" if default else "0") == "0":
         return False
     if ops.compute_bf16() != 0:
         return False
-    ext = ops._load_extension()
-    weights, _, _ = _extract_layers(fop._mlp_of(policy))
-    O, A = int(env.A.shape[0]), int(env.B.shape[0])
+    max_layers, max_width, *max_cuts, max_lds = limits
+    if cuts is not None and max_cuts and len(cuts) > max_cuts[0]:
+        return False
+    if weights is None:
+        return True
     dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
-    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
-    max_layers, max_width, max_cuts, max_lds = ext.ppo_rollout_fused_limits()
-    if (len(weights) > max_layers or max(dims) > max_width or dims[0] != O
-            or dims[-1] != A or policy.log_std.numel() != A
-            or len(cuts) > max_cuts):
+    if (len(weights) > max_layers or max(dims) > max_width or dims[0] != in_dim
+            or (out_dim is not None and dims[-1] != out_dim)):
         return False
-    if any(t.dtype != torch.float32 for t in (*weights, policy.log_std)):
+    if any(t.dtype != torch.float32 for t in (*weights, *extra_fp32)):
         return False
-    return ext.ppo_rollout_fused_lds_bytes(dims, O, A) <= max_lds
+    return lds_bytes(dims) <= max_lds
+
+
+def _weights_of(policy):
+    return _extract_layers(fop._mlp_of(policy))[0]
 
 
 def make_counter(device) -> torch.Tensor:
     """Device RNG counter; base 2^40 keeps the graph streams clear of the
     host-side offsets the eager paths use under the same seeds."""
     return torch.full((1,), 1 << 40, dtype=torch.int64, device=device)
+
+
+# ---------------------------------------------------------------------------
+# The multi-kernel step loops
+# ---------------------------------------------------------------------------
+def _pendulum_epoch(ext, state, env_seed, steps: int, cuts, action, reset,
+                    ctr, obs_full, rew_buf, cut_final, fin_scratch,
+                    after_reset=None) -> None:
+    """Issue pendulum_env_reset, then steps x (`action(t)` ->
+    pendulum_env_step) on the fp64 carry `state`.  `reset` is (Philox
+    offset, counter, draw a fresh state?); `action(t)` issues the step's
+    action kernels and returns the [N, 1] action.  A cut step writes its
+    true successor to `cut_final[slot]`; every other step's successor equals
+    obs_full[t + 1], and the kernel still writes it somewhere:
+    `fin_scratch`."""
+    offset, reset_ctr, fresh = reset
+    ext.pendulum_env_reset(state, env_seed, offset, reset_ctr, obs_full[0], fresh)
+    if after_reset is not None:
+        after_reset()
+    cset = {c: j for j, c in enumerate(cuts)}
+    for t in range(steps):
+        act = action(t)
+        do_reset = t in cset
+        ext.pendulum_env_step(
+            state, act, do_reset, env_seed, t, ctr, obs_full[t + 1],
+            cut_final[cset[t]] if do_reset else fin_scratch, rew_buf[t],
+        )
+
+
+def _cartpole_epoch(ext, net, seeds, state, elapsed, max_steps: int, steps: int,
+                    reset, ctr, obs_full, finals, act_buf, rew_buf, done_buf,
+                    after_reset=None) -> None:
+    """Issue cartpole_env_reset (`reset` = (Philox offset, counter)) or, with
+    `reset` None, the copy of the carried state, then steps x (mlp_forward
+    -> categorical_sample -> cartpole_env_step).  `finals[t]` takes step t's
+    pre-autoreset successor."""
+    weights, biases, acts = net
+    policy_seed, env_seed = seeds
+    compute_bf16 = ops.compute_bf16()
+    if reset is not None:
+        ext.cartpole_env_reset(state, elapsed, env_seed, *reset, obs_full[0])
+    else:
+        obs_full[0].copy_(state)
+    if after_reset is not None:
+        after_reset()
+    for t in range(steps):
+        logits = ext.mlp_forward(obs_full[t], list(weights), list(biases), acts,
+                                 False, compute_bf16)[0]
+        ext.categorical_sample(logits, policy_seed, t, ctr, act_buf[t])
+        ext.cartpole_env_step(
+            state, elapsed, act_buf[t], max_steps, env_seed, t, ctr,
+            obs_full[t + 1], finals[t], rew_buf[t], done_buf[t],
+        )
+
+
+# ---------------------------------------------------------------------------
+# Gaussian policy on the synthetic envs (DeviceSampler)
+# ---------------------------------------------------------------------------
+def supported(policy, env) -> bool:
+    from rl_replicas_amd.envs.device import DeviceVectorEnv
+
+    return _graph_supported(policy, env, DeviceVectorEnv, "gaussian")
+
+
+def fused_kernel_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
+    """ppo_rollout_fused (rollout_fused_kernels.hip) takes the epoch: a
+    Gaussian policy without action clipping (the only kind `supported`
+    admits), every width and the obs dim <= 64, one log_std per action."""
+    ext = ops._load_extension()
+    O, A = int(env.A.shape[0]), int(env.B.shape[0])
+    return policy.log_std.numel() == A and _fused_gate(
+        _weights_of(policy), [policy.log_std], ext.ppo_rollout_fused_limits(),
+        lambda dims: ext.ppo_rollout_fused_lds_bytes(dims, O, A), O, A, cuts)
 
 
 class GraphedRollout:
@@ -196,46 +268,23 @@ class GraphedRollout:
 # Categorical policy on the device CartPole env (DeviceEpisodicSampler)
 # ---------------------------------------------------------------------------
 def cartpole_supported(policy, env) -> bool:
-    """A CategoricalPolicy over an MLP on a GPU DeviceCartPoleEnv, with the
-    extension present and graphs enabled."""
     from rl_replicas_amd.envs.device import DeviceCartPoleEnv
 
-    if not (isinstance(env, DeviceCartPoleEnv) and env.device.type == "cuda"
-            and ops.hip_available() and fop._graphs_common(None)
-            and fop._policy_kind(policy) == "categorical"):
-        return False
-    mlp = fop._mlp_of(policy)
-    return mlp is not None and _extract_layers(mlp) is not None
+    return _graph_supported(policy, env, DeviceCartPoleEnv, "categorical")
 
 
 def cartpole_fused_eligible(policy, env) -> bool:
-    """Whether the epoch runs as ONE persistent kernel (cartpole_rollout_fused,
-    cartpole_rollout_kernels.hip) instead of steps x 3 kernels: fp32 compute,
-    every width <= 64, the net image within the kernel's LDS budget.
-    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
-    import os
-
-    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
-        return False
-    if ops.compute_bf16() != 0:
-        return False
+    """cartpole_rollout_fused (cartpole_rollout_kernels.hip) takes the epoch:
+    a net [4, ...] with every width <= 64."""
     ext = ops._load_extension()
-    weights, _, _ = _extract_layers(fop._mlp_of(policy))
-    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
-    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
-    max_layers, max_width, max_lds = ext.cartpole_rollout_fused_limits()
-    if len(weights) > max_layers or max(dims) > max_width or dims[0] != 4:
-        return False
-    if any(w.dtype != torch.float32 for w in weights):
-        return False
-    return ext.cartpole_rollout_fused_lds_bytes(dims) <= max_lds
+    return _fused_gate(_weights_of(policy), (), ext.cartpole_rollout_fused_limits(),
+                       ext.cartpole_rollout_fused_lds_bytes, 4)
 
 
 class GraphedCartPoleRollout:
-    """One captured epoch on a DeviceCartPoleEnv: [cartpole_env_reset |
-    nothing] + steps x (mlp_forward -> categorical_sample ->
-    cartpole_env_step) + counter bump; or, when `cartpole_fused_eligible`,
-    cartpole_rollout_fused + counter bump.
+    """One captured epoch on a DeviceCartPoleEnv: `_cartpole_epoch` + counter
+    bump; or, when `cartpole_fused_eligible`, cartpole_rollout_fused +
+    counter bump.
 
     Termination, truncation and autoreset are decided in-kernel, so there is
     one graph per (steps, start_with_reset) and no cut patterns.  The env's
@@ -261,8 +310,7 @@ class GraphedCartPoleRollout:
         policy_seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
         env_seed = env._philox_seed
         max_steps = env.max_steps
-        weights, biases, acts = _extract_layers(fop._mlp_of(policy))
-        compute_bf16 = ops.compute_bf16()
+        net = weights, biases, acts = _extract_layers(fop._mlp_of(policy))
 
         self.fused = cartpole_fused_eligible(policy, env)
 
@@ -276,21 +324,12 @@ class GraphedCartPoleRollout:
             ext.counter_add_(self.ctr, steps + 1)
 
         def body():
-            if start_with_reset:
-                ext.cartpole_env_reset(env.state, env.elapsed, env_seed, steps,
-                                       self.ctr, self.obs_full[0])
-            else:
-                self.obs_full[0].copy_(env.state)
-            for t in range(steps):
-                logits = ext.mlp_forward(self.obs_full[t], list(weights),
-                                         list(biases), acts, False, compute_bf16)[0]
-                ext.categorical_sample(logits, policy_seed, t, self.ctr,
-                                       self.act_buf[t])
-                ext.cartpole_env_step(
-                    env.state, env.elapsed, self.act_buf[t], max_steps, env_seed,
-                    t, self.ctr, self.obs_full[t + 1], self.final_obs[t],
-                    self.rew_buf[t], self.done_buf[t],
-                )
+            _cartpole_epoch(
+                ext, net, (policy_seed, env_seed), env.state, env.elapsed,
+                max_steps, steps, (steps, self.ctr) if start_with_reset else None,
+                self.ctr, self.obs_full, self.final_obs, self.act_buf,
+                self.rew_buf, self.done_buf,
+            )
             # past every offset used: sample/autoreset t (t<steps), reset steps
             ext.counter_add_(self.ctr, steps + 1)
 
@@ -307,48 +346,24 @@ class GraphedCartPoleRollout:
 # Gaussian policy on the device Pendulum env (DeviceSampler)
 # ---------------------------------------------------------------------------
 def pendulum_supported(policy, env) -> bool:
-    """A GaussianPolicy over an MLP on a GPU DevicePendulumEnv, with the
-    extension present and graphs enabled."""
     from rl_replicas_amd.envs.device import DevicePendulumEnv
 
-    if not (isinstance(env, DevicePendulumEnv) and env.device.type == "cuda"
-            and ops.hip_available() and fop._graphs_common(None)
-            and fop._policy_kind(policy) == "gaussian"):
-        return False
-    mlp = fop._mlp_of(policy)
-    return mlp is not None and _extract_layers(mlp) is not None
+    return _graph_supported(policy, env, DevicePendulumEnv, "gaussian")
 
 
 def pendulum_fused_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
-    """Whether the epoch runs as ONE persistent kernel (pendulum_rollout_fused,
-    pendulum_rollout_kernels.hip) instead of steps x 3 kernels: fp32 compute
-    and weights, a net [3, ..., 1] with every width <= 64, one log_std, the
-    cut list and the net image within the kernel's limits.
-    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
-    import os
-
-    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", "1") == "0":
-        return False
-    if ops.compute_bf16() != 0:
-        return False
+    """pendulum_rollout_fused (pendulum_rollout_kernels.hip) takes the epoch:
+    a net [3, ..., 1] with every width <= 64, one log_std, the cut list
+    within the by-value limit."""
     ext = ops._load_extension()
-    weights, _, _ = _extract_layers(fop._mlp_of(policy))
-    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
-    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
-    max_layers, max_width, max_cuts, max_lds = ext.pendulum_rollout_fused_limits()
-    if (len(weights) > max_layers or max(dims) > max_width or dims[0] != 3
-            or dims[-1] != 1 or policy.log_std.numel() != 1
-            or len(cuts) > max_cuts):
-        return False
-    if any(t.dtype != torch.float32 for t in (*weights, policy.log_std)):
-        return False
-    return ext.pendulum_rollout_fused_lds_bytes(dims) <= max_lds
+    return policy.log_std.numel() == 1 and _fused_gate(
+        _weights_of(policy), [policy.log_std], ext.pendulum_rollout_fused_limits(),
+        ext.pendulum_rollout_fused_lds_bytes, 3, 1, cuts)
 
 
 class GraphedPendulumRollout:
-    """One captured epoch on a DevicePendulumEnv: [pendulum_env_reset | the
-    observation of the carried state] + steps x (mlp_forward ->
-    gaussian_sample -> pendulum_env_step) + counter bump; or, when
+    """One captured epoch on a DevicePendulumEnv: `_pendulum_epoch` with a
+    Gaussian sample as the action + counter bump; or, when
     `pendulum_fused_eligible`, pendulum_rollout_fused + counter bump.
 
     Pendulum is lockstep, so the graph is keyed (steps, cuts,
@@ -378,7 +393,6 @@ class GraphedPendulumRollout:
         state = env.state  # the env's in-place carry
         weights, biases, acts = _extract_layers(fop._mlp_of(policy))
         log_std = policy.log_std
-        cset = {c: j for j, c in enumerate(cuts)}
         compute_bf16 = ops.compute_bf16()
 
         self.fused = pendulum_fused_eligible(policy, env, cuts)
@@ -391,25 +405,19 @@ class GraphedPendulumRollout:
             )
             ext.counter_add_(self.ctr, steps + 1)
 
-        # non-cut steps' successor rows equal obs_full[t + 1]; the kernel
-        # still writes them somewhere
         fin_scratch = torch.zeros(N, 3, device=dev)
 
+        def action(t):
+            mean = ext.mlp_forward(self.obs_full[t], list(weights), list(biases),
+                                   acts, False, compute_bf16)[0]
+            ext.gaussian_sample(mean, log_std.data, policy_seed, t, -1.0, -1.0,
+                                self.ctr, self.act_buf[t])
+            return self.act_buf[t]
+
         def body():
-            ext.pendulum_env_reset(state, env_seed, steps, self.ctr,
-                                   self.obs_full[0], start_with_reset)
-            for t in range(steps):
-                mean = ext.mlp_forward(self.obs_full[t], list(weights),
-                                       list(biases), acts, False, compute_bf16)[0]
-                ext.gaussian_sample(mean, log_std.data, policy_seed, t, -1.0,
-                                    -1.0, self.ctr, self.act_buf[t])
-                do_reset = t in cset
-                ext.pendulum_env_step(
-                    state, self.act_buf[t], do_reset, env_seed, t, self.ctr,
-                    self.obs_full[t + 1],
-                    self.cut_final[cset[t]] if do_reset else fin_scratch,
-                    self.rew_buf[t],
-                )
+            _pendulum_epoch(ext, state, env_seed, steps, cuts, action,
+                            (steps, self.ctr, start_with_reset), self.ctr,
+                            self.obs_full, self.rew_buf, self.cut_final, fin_scratch)
             # past every offset used: sample/autoreset t (t<steps), reset steps
             ext.counter_add_(self.ctr, steps + 1)
 
@@ -483,8 +491,7 @@ def pendulum_collect_supported(policy, env, buffer) -> bool:
     graphs enabled."""
     from rl_replicas_amd.envs.device import DevicePendulumEnv
 
-    if not (isinstance(env, DevicePendulumEnv) and env.device.type == "cuda"
-            and ops.hip_available() and fop._graphs_common(None)):
+    if not _env_ready(env, DevicePendulumEnv):
         return False
     if buffer is None or buffer.device is None or buffer.device.type != "cuda":
         return False
@@ -505,40 +512,23 @@ def collect_wide_threads() -> int:
     """Workgroup size of the persistent kernel's wide regime: 1024 (one
     column tile per wave at width 256), the measured default, or 256 (four
     tiles per wave) with RL_REPLICAS_AMD_COLLECT_WG=256."""
-    import os
-
     return 256 if os.environ.get("RL_REPLICAS_AMD_COLLECT_WG", "1024") == "256" else 1024
 
 
 def pendulum_collect_fused_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
-    """Whether a collect epoch runs as ONE persistent kernel
-    (pendulum_collect_fused, pendulum_collect_kernels.hip) instead of the
-    multi-kernel body: fp32 compute and weights, an actor [3, ..., 1] and a
-    cut list within the binding's own limits.
-    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
-    import os
-
-    default = "1" if collect_fused_default() else "0"
-    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", default) == "0":
-        return False
-    if ops.compute_bf16() != 0:
-        return False
-    ext = ops._load_extension()
-    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
-    max_layers, max_width, max_cuts, max_lds = ext.pendulum_collect_fused_limits()
-    if len(cuts) > max_cuts:
-        return False
-    # an fp32 actor [3, ..., 1] on the env's device, or no net at all
+    """pendulum_collect_fused (pendulum_collect_kernels.hip) takes the collect
+    epoch: an actor [3, ..., 1], or no net at all (the uniform draw), and a
+    cut list within the binding's own limits."""
     mode = pendulum_collect_mode(policy, env)
     if mode is None:
         return False
-    if mode == COLLECT_UNIFORM:
-        return True
-    weights, _, _ = _extract_layers(fop._mlp_of(policy.base_policy))
-    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
-    if len(weights) > max_layers or max(dims) > max_width:
-        return False
-    return ext.pendulum_collect_fused_lds_bytes(dims) <= max_lds
+    ext = ops._load_extension()
+    # COLLECT_NOISED already means fp32 weights and biases [3, ..., 1], so the
+    # gate's own dtype and width checks cannot change the answer here
+    weights = _weights_of(policy.base_policy) if mode == COLLECT_NOISED else None
+    return _fused_gate(weights, (), ext.pendulum_collect_fused_limits(),
+                       ext.pendulum_collect_fused_lds_bytes, 3, 1, cuts,
+                       default=collect_fused_default())
 
 
 class GraphedPendulumCollect:
@@ -547,10 +537,10 @@ class GraphedPendulumCollect:
     buffer holds on the device.
 
     Fused body (`pendulum_collect_fused_eligible`): pendulum_collect_fused,
-    ring_advance_, counter_add_.  Multi-kernel body: pendulum_env_reset,
-    steps x ([mlp_forward -> gaussian_sample with noise scale / limit] |
-    uniform_sample, then pendulum_env_step), replay_scatter, ring_advance_,
-    counter_add_.  Both write the same bytes.
+    ring_advance_, counter_add_.  Multi-kernel body: `_pendulum_epoch` whose
+    action is [mlp_forward -> gaussian_sample with noise scale / limit] or
+    uniform_sample, then replay_scatter, ring_advance_, counter_add_.  Both
+    write the same bytes.
 
     Keyed (steps, cuts, start_with_reset, mode) by the sampler.  Philox
     offsets (both bodies): action and autoreset of step t at `t + ctr`
@@ -581,7 +571,6 @@ class GraphedPendulumCollect:
         state = env.state  # the env's in-place carry
         env_seed = env._philox_seed
         base_seed = torch.initial_seed()
-        cset = {c: j for j, c in enumerate(cuts)}
         compute_bf16 = ops.compute_bf16()
         low = float(env.action_space.low.reshape(-1)[0])
         high = float(env.action_space.high.reshape(-1)[0])
@@ -618,30 +607,28 @@ class GraphedPendulumCollect:
             self.rew_buf = torch.zeros(steps, N, device=dev)
             self.cut_final = torch.zeros(max(len(cuts), 1), N, 3, device=dev)
             self.last_obs = self.obs_full[steps]
-            cut_slot = torch.tensor([cset.get(t, -1) for t in range(steps)],
-                                    dtype=torch.int32, device=dev)
+            cut_slot = torch.tensor(
+                [cuts.index(t) if t in cuts else -1 for t in range(steps)],
+                dtype=torch.int32, device=dev)
             fin_scratch = torch.zeros(N, 3, device=dev)
 
+            def action(t):
+                if mode == COLLECT_NOISED:
+                    mean = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                           acts, False, compute_bf16)[0]
+                    ext.gaussian_sample(mean, dummy_log_std, action_seed, t,
+                                        noise_scale, limit, self.ctr,
+                                        self.act_buf[t])
+                else:
+                    ext.uniform_sample(self.act_buf[t], low, high, action_seed,
+                                       t, self.ctr)
+                return self.act_buf[t]
+
             def body():
-                ext.pendulum_env_reset(state, env_seed, steps, self.ctr,
-                                       self.obs_full[0], start_with_reset)
-                for t in range(steps):
-                    if mode == COLLECT_NOISED:
-                        mean = ext.mlp_forward(self.obs_full[t], weights, biases,
-                                               acts, False, compute_bf16)[0]
-                        ext.gaussian_sample(mean, dummy_log_std, action_seed, t,
-                                            noise_scale, limit, self.ctr,
-                                            self.act_buf[t])
-                    else:
-                        ext.uniform_sample(self.act_buf[t], low, high, action_seed,
-                                           t, self.ctr)
-                    do_reset = t in cset
-                    ext.pendulum_env_step(
-                        state, self.act_buf[t], do_reset, env_seed, t, self.ctr,
-                        self.obs_full[t + 1],
-                        self.cut_final[cset[t]] if do_reset else fin_scratch,
-                        self.rew_buf[t],
-                    )
+                _pendulum_epoch(ext, state, env_seed, steps, cuts, action,
+                                (steps, self.ctr, start_with_reset), self.ctr,
+                                self.obs_full, self.rew_buf, self.cut_final,
+                                fin_scratch)
                 ext.replay_scatter(self.obs_full, self.act_buf, self.rew_buf,
                                    self.cut_final, cut_slot, len(cuts), storage,
                                    write_dev, size_dev, self.seg_returns)
@@ -699,59 +686,37 @@ def eval_fused_default(kind: str) -> bool:
     return True
 
 
-def _eval_fused_common(policy, kind: str, ext, limits, lds_bytes, in_dim: int) -> bool:
-    import os
-
-    default = "1" if eval_fused_default(kind) else "0"
-    if os.environ.get("RL_REPLICAS_AMD_ROLLOUT_FUSED", default) == "0":
-        return False
-    if ops.compute_bf16() != 0:
-        return False
-    weights, biases, _ = _extract_layers(fop._mlp_of(policy))
-    dims = [int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights]
-    # the binding's own limits (common.h), so gate and TORCH_CHECKs agree
-    max_layers, max_width, max_lds = limits
-    if len(weights) > max_layers or max(dims) > max_width or dims[0] != in_dim:
-        return False
-    if any(t.dtype != torch.float32 for t in (*weights, *biases)):
-        return False
-    return lds_bytes(dims) <= max_lds
-
-
 def pendulum_eval_fused_eligible(policy) -> bool:
-    """Whether a Pendulum evaluation runs as ONE persistent kernel
-    (pendulum_eval_fused, eval_kernels.hip) instead of the multi-kernel
-    body: fp32 compute and parameters, a net [3, ..., 1] within the binding's
-    own limits, one log_std for a Gaussian policy.
-    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    """pendulum_eval_fused (eval_kernels.hip) takes the evaluation: fp32
+    parameters, a net [3, ..., 1] within the binding's own limits, one fp32
+    log_std for a Gaussian policy."""
     mode = pendulum_eval_mode(policy)
     if mode is None:
-        return False
-    ext = ops._load_extension()
-    weights, _, _ = _extract_layers(fop._mlp_of(policy))
-    if int(weights[-1].shape[0]) != 1:
         return False
     if mode == EVAL_GAUSSIAN and (policy.log_std.numel() != 1
                                   or policy.log_std.dtype != torch.float32):
         return False
-    return _eval_fused_common(policy, "pendulum", ext, ext.pendulum_eval_fused_limits(),
-                              ext.pendulum_eval_fused_lds_bytes, 3)
+    ext = ops._load_extension()
+    weights, biases, _ = _extract_layers(fop._mlp_of(policy))
+    return _fused_gate(weights, biases, ext.pendulum_eval_fused_limits(),
+                       ext.pendulum_eval_fused_lds_bytes, 3, 1,
+                       default=eval_fused_default("pendulum"))
 
 
 def cartpole_eval_fused_eligible(policy) -> bool:
-    """Whether a CartPole evaluation runs as ONE persistent kernel
-    (cartpole_eval_fused, eval_kernels.hip) instead of the multi-kernel
-    body: fp32 compute and parameters, a categorical net [4, ..., n_act]
-    with every width <= 64, within the binding's own limits.
-    RL_REPLICAS_AMD_ROLLOUT_FUSED=0 selects the multi-kernel body."""
+    """cartpole_eval_fused (eval_kernels.hip) takes the evaluation: fp32
+    parameters, a categorical net [4, ..., n_act] with every width <= 64,
+    within the binding's own limits."""
     if fop._policy_kind(policy) != "categorical":
         return False
     mlp = fop._mlp_of(policy)
     if mlp is None or _extract_layers(mlp) is None:
         return False
     ext = ops._load_extension()
-    return _eval_fused_common(policy, "cartpole", ext, ext.cartpole_eval_fused_limits(),
-                              ext.cartpole_eval_fused_lds_bytes, 4)
+    weights, biases, _ = _extract_layers(mlp)
+    return _fused_gate(weights, biases, ext.cartpole_eval_fused_limits(),
+                       ext.cartpole_eval_fused_lds_bytes, 4,
+                       default=eval_fused_default("cartpole"))
 
 
 class _GraphedEval:
@@ -800,11 +765,11 @@ class GraphedPendulumEval(_GraphedEval):
     `horizon` steps.
 
     Fused body (`pendulum_eval_fused_eligible`): pendulum_eval_fused, then
-    the counter bumps.  Multi-kernel body: pendulum_env_reset into a private
-    state tensor (copied to `init_state`), horizon x (mlp_forward ->
-    [gaussian_sample] -> pendulum_env_step), episode_reduce, the counter
-    bumps; it keeps `act_buf` [horizon, N, 1].  Both write the same bytes to
-    `returns`, `lengths` and `init_state`."""
+    the counter bumps.  Multi-kernel body: `_pendulum_epoch` without cuts on
+    a private state tensor (copied to `init_state` after the reset), the
+    action being the mean itself or a Gaussian sample around it, then
+    episode_reduce and the counter bumps; it keeps `act_buf` [horizon, N, 1].
+    Both write the same bytes to `returns`, `lengths` and `init_state`."""
 
     state_dim = 2
 
@@ -841,28 +806,26 @@ class GraphedPendulumEval(_GraphedEval):
             self.rew_buf = torch.zeros(horizon, N, device=dev)
             if gaussian:
                 self._act_buf = torch.zeros(horizon, N, 1, device=dev)
-            # the step kernel's successor rows: unused, but the graph writes
-            # them on every replay, so the storage lives as long as the graph
-            self._fin_scratch = fin_scratch = torch.zeros(N, 3, device=dev)
+            fin_scratch = torch.zeros(N, 3, device=dev)
             self._means: List[torch.Tensor] = []
 
             def body():
                 means = []
-                ext.pendulum_env_reset(self.state, env_seed, 0, self.reset_ctr,
-                                       self.obs_full[0], True)
-                self.init_state.copy_(self.state)
-                for t in range(horizon):
-                    action = ext.mlp_forward(self.obs_full[t], weights, biases,
-                                             acts, False, compute_bf16)[0]
-                    if gaussian:
-                        ext.gaussian_sample(action, log_std.data, policy_seed, t,
-                                            -1.0, -1.0, self.ctr, self._act_buf[t])
-                        action = self._act_buf[t]
-                    else:
-                        means.append(action)  # the deterministic action itself
-                    ext.pendulum_env_step(self.state, action, False, env_seed, t,
-                                          self.ctr, self.obs_full[t + 1],
-                                          fin_scratch, self.rew_buf[t])
+
+                def action(t):
+                    mean = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                           acts, False, compute_bf16)[0]
+                    if not gaussian:
+                        means.append(mean)  # the deterministic action itself
+                        return mean
+                    ext.gaussian_sample(mean, log_std.data, policy_seed, t,
+                                        -1.0, -1.0, self.ctr, self._act_buf[t])
+                    return self._act_buf[t]
+
+                _pendulum_epoch(ext, self.state, env_seed, horizon, (), action,
+                                (0, self.reset_ctr, True), self.ctr,
+                                self.obs_full, self.rew_buf, None, fin_scratch,
+                                after_reset=lambda: self.init_state.copy_(self.state))
                 ext.episode_reduce(self.rew_buf, None, self.returns, self.lengths)
                 self._bump(ext)
                 self._means = means  # the captured run's outputs
@@ -883,12 +846,11 @@ class GraphedCartPoleEval(_GraphedEval):
 
     Fused body (`cartpole_eval_fused_eligible`): cartpole_eval_fused, which
     stops stepping once every row of a workgroup has finished, then the
-    counter bumps.  Multi-kernel body: cartpole_env_reset into private carry
-    tensors (state copied to `init_state`), horizon x (mlp_forward ->
-    categorical_sample -> cartpole_env_step with autoreset), episode_reduce
-    over each row's first episode, the counter bumps; it keeps `act_buf`
-    [horizon, N].  Both write the same bytes to `returns`, `lengths` and
-    `init_state`."""
+    counter bumps.  Multi-kernel body: `_cartpole_epoch` (with autoreset) on
+    private carry tensors (state copied to `init_state` after the reset),
+    episode_reduce over each row's first episode, the counter bumps; it
+    keeps `act_buf` [horizon, N].  Both write the same bytes to `returns`,
+    `lengths` and `init_state`."""
 
     state_dim = 4
 
@@ -902,7 +864,6 @@ class GraphedCartPoleEval(_GraphedEval):
         weights, biases, acts = _extract_layers(fop._mlp_of(policy))
         weights, biases = list(weights), list(biases)
         policy_seed = self.policy_seed
-        compute_bf16 = ops.compute_bf16()
 
         self.fused = cartpole_eval_fused_eligible(policy)
 
@@ -921,23 +882,17 @@ class GraphedCartPoleEval(_GraphedEval):
             self.act_buf = torch.zeros(horizon, N, dtype=torch.int64, device=dev)
             self.rew_buf = torch.zeros(horizon, N, device=dev)
             self.done_buf = torch.zeros(horizon, N, dtype=torch.uint8, device=dev)
-            # unused successor rows the graph writes on every replay
-            self._fin_scratch = fin_scratch = torch.zeros(N, 4, device=dev)
+            # the successor rows are unused: every step writes the same one
+            finals = [torch.zeros(N, 4, device=dev)] * horizon
 
             def body():
-                ext.cartpole_env_reset(self.state, self.elapsed, env_seed, 0,
-                                       self.reset_ctr, self.obs_full[0])
-                self.init_state.copy_(self.state)
-                for t in range(horizon):
-                    logits = ext.mlp_forward(self.obs_full[t], weights, biases,
-                                             acts, False, compute_bf16)[0]
-                    ext.categorical_sample(logits, policy_seed, t, self.ctr,
-                                           self.act_buf[t])
-                    ext.cartpole_env_step(
-                        self.state, self.elapsed, self.act_buf[t], horizon,
-                        env_seed, t, self.ctr, self.obs_full[t + 1], fin_scratch,
-                        self.rew_buf[t], self.done_buf[t],
-                    )
+                _cartpole_epoch(
+                    ext, (weights, biases, acts), (policy_seed, env_seed),
+                    self.state, self.elapsed, horizon, horizon,
+                    (0, self.reset_ctr), self.ctr, self.obs_full, finals,
+                    self.act_buf, self.rew_buf, self.done_buf,
+                    after_reset=lambda: self.init_state.copy_(self.state),
+                )
                 ext.episode_reduce(self.rew_buf, self.done_buf, self.returns,
                                    self.lengths)
                 self._bump(ext)

@@ -30,6 +30,7 @@ import torch
 
 from rl_replicas_amd.experience import Experience
 from rl_replicas_amd.policies import Policy
+from rl_replicas_amd.samplers.device_sampler import cached_graph
 from rl_replicas_amd.samplers.sampler import Sampler
 
 
@@ -68,16 +69,11 @@ class DeviceEpisodicSampler(Sampler):
     def _sample_graphed(self, policy, steps: int, reset_epoch: bool):
         from rl_replicas_amd.ops import fused_rollout
 
-        env = self.env
-        if self._graph_ctr is None:
-            self._graph_ctr = fused_rollout.make_counter(env.device)
-        key = (steps, reset_epoch)
-        g = self._graphs.get(key)
-        if g is None:
-            g = fused_rollout.GraphedCartPoleRollout(
-                policy, env, steps, reset_epoch, self._graph_ctr
-            )
-            self._graphs[key] = g
+        g = cached_graph(
+            self, (steps, reset_epoch),
+            lambda ctr: fused_rollout.GraphedCartPoleRollout(
+                policy, self.env, steps, reset_epoch, ctr),
+        )
         # the carry (env.state / env.elapsed) is read and written in place
         g.replay()
         self._obs = g.obs_full[steps]

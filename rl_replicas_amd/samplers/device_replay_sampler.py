@@ -33,7 +33,12 @@ from rl_replicas_amd.envs.device import DevicePendulumEnv
 from rl_replicas_amd.experience import Experience
 from rl_replicas_amd.policies import Policy
 from rl_replicas_amd.replay_buffer import ReplayBuffer
-from rl_replicas_amd.samplers.device_sampler import DeviceSampler
+from rl_replicas_amd.samplers.device_sampler import (
+    DeviceSampler,
+    cached_graph,
+    lockstep_cuts,
+    segment_bounds,
+)
 
 
 class DeviceReplaySampler(DeviceSampler):
@@ -63,11 +68,7 @@ class DeviceReplaySampler(DeviceSampler):
         first = self._obs is None
         horizon = env.spec.max_episode_steps
         start_elapsed = 0 if first else env._elapsed
-        # lockstep truncation boundaries are pure host arithmetic
-        cuts: Tuple[int, ...] = tuple(
-            t for t in range(steps)
-            if horizon is not None and (start_elapsed + t + 1) % horizon == 0
-        )
+        cuts = lockstep_cuts(steps, horizon, start_elapsed)
         mode = fused_rollout.pendulum_collect_mode(policy, env)
         key = (steps, cuts, first, mode)
         g = self._graphs.get(key)
@@ -76,12 +77,11 @@ class DeviceReplaySampler(DeviceSampler):
                 return super().sample(num_samples, policy)
             if first and self.seed is not None:
                 env.seed(self.seed)
-            if self._graph_ctr is None:
-                self._graph_ctr = fused_rollout.make_counter(env.device)
-            g = fused_rollout.GraphedPendulumCollect(
-                policy, env, buffer, steps, cuts, first, mode, self._graph_ctr
+            g = cached_graph(
+                self, key,
+                lambda ctr: fused_rollout.GraphedPendulumCollect(
+                    policy, env, buffer, steps, cuts, first, mode, ctr),
             )
-            self._graphs[key] = g
         g.replay()
         self._obs = g.last_obs
         env._elapsed = steps - (cuts[-1] + 1) if cuts else start_elapsed + steps
@@ -90,22 +90,16 @@ class DeviceReplaySampler(DeviceSampler):
     def _build_marked_experience(self, steps: int, cuts: Tuple[int, ...],
                                  seg_returns) -> Experience:
         N = self.num_envs
-        bounds = []  # (length, done), as in DeviceSampler._build_experience
-        start = 0
-        for c in cuts:
-            bounds.append((c + 1 - start, True))
-            start = c + 1
-        if start < steps:
-            bounds.append((steps - start, False))
+        bounds = segment_bounds(steps, cuts)  # as in DeviceSampler._build_experience
         experience = Experience()
         # one tiny D2H: per-episode returns for the metrics layer
         experience.episode_returns = [
             float(r) for r in seg_returns.cpu().numpy().reshape(-1)
         ]
-        experience.episode_lengths = [length for length, _ in bounds] * N
+        experience.episode_lengths = [e - s for s, e, _ in bounds] * N
         experience.dones = [
-            np.concatenate([np.zeros(length - 1, dtype=bool), [done]])
-            for length, done in bounds
+            np.concatenate([np.zeros(e - s - 1, dtype=bool), [done]])
+            for s, e, done in bounds
         ] * N
         experience.stored_in_buffer = self.replay_buffer
         return experience

@@ -39,6 +39,41 @@ from rl_replicas_amd.policies import Policy
 from rl_replicas_amd.samplers.sampler import Sampler
 
 
+def lockstep_cuts(steps: int, horizon: Optional[int], start_elapsed: int) -> Tuple[int, ...]:
+    """The steps of an epoch after which every instance truncates.  The env
+    is lockstep, so the boundaries are pure host arithmetic."""
+    if horizon is None:
+        return ()
+    return tuple(t for t in range(steps) if (start_elapsed + t + 1) % horizon == 0)
+
+
+def segment_bounds(steps: int, cuts: Tuple[int, ...]) -> List[tuple]:
+    """(start, end_exclusive, done) of an epoch's episodes per instance: one
+    done segment per cut, then the open one the epoch end cuts, if any."""
+    bounds: List[tuple] = []
+    start = 0
+    for c in cuts:
+        bounds.append((start, c + 1, True))
+        start = c + 1
+    if start < steps:
+        bounds.append((start, steps, False))
+    return bounds
+
+
+def cached_graph(sampler, key: tuple, build):
+    """`sampler._graphs[key]`, or `build(ctr)` stored there; `ctr` is the
+    sampler's one device RNG counter, shared by all of its graphs so that
+    switching graphs never reuses (seed, offset) pairs, made on first use."""
+    g = sampler._graphs.get(key)
+    if g is None:
+        if sampler._graph_ctr is None:
+            from rl_replicas_amd.ops import fused_rollout
+
+            sampler._graph_ctr = fused_rollout.make_counter(sampler.env.device)
+        g = sampler._graphs[key] = build(sampler._graph_ctr)
+    return g
+
+
 class DeviceSampler(Sampler):
     def __init__(self, device_env: DeviceVectorEnv, seed: Optional[int] = None, is_continuous: bool = False):
         self.env = device_env
@@ -75,11 +110,7 @@ class DeviceSampler(Sampler):
         reset_epoch = first or not self.is_continuous
         horizon = env.spec.max_episode_steps
         start_elapsed = 0 if reset_epoch else env._elapsed
-        # lockstep truncation boundaries are pure host arithmetic
-        cuts: Tuple[int, ...] = tuple(
-            t for t in range(steps)
-            if horizon is not None and (start_elapsed + t + 1) % horizon == 0
-        )
+        cuts = lockstep_cuts(steps, horizon, start_elapsed)
 
         from rl_replicas_amd.ops import fused_rollout
 
@@ -95,9 +126,7 @@ class DeviceSampler(Sampler):
         if graph_ok:
             if first and self.seed is not None:
                 env.seed(self.seed)
-            sample_graphed = (self._sample_graphed_pendulum if pendulum
-                              else self._sample_graphed)
-            obs_buf, act_buf, rew_buf, finals = sample_graphed(
+            obs_buf, act_buf, rew_buf, finals = self._sample_graphed(
                 policy, steps, cuts, reset_epoch
             )
         else:
@@ -116,44 +145,24 @@ class DeviceSampler(Sampler):
         from rl_replicas_amd.ops import fused_rollout
 
         env = self.env
-        if self._graph_ctr is None:
-            self._graph_ctr = fused_rollout.make_counter(env.device)
-        key = (steps, cuts, reset_epoch)
-        g = self._graphs.get(key)
-        if g is None:
-            g = fused_rollout.GraphedRollout(
-                policy, env, steps, cuts, reset_epoch, self._graph_ctr
-            )
-            self._graphs[key] = g
-        if not reset_epoch:
+        # DevicePendulumEnv carries its own fp64 `state` between epochs, which
+        # the kernels read and write in place; the synthetic envs' carry is
+        # the observation itself, in the graph's last row
+        pendulum = isinstance(env, DevicePendulumEnv)
+        cls = (fused_rollout.GraphedPendulumRollout if pendulum
+               else fused_rollout.GraphedRollout)
+        g = cached_graph(
+            self, (steps, cuts, reset_epoch),
+            lambda ctr: cls(policy, env, steps, cuts, reset_epoch, ctr),
+        )
+        if not pendulum and not reset_epoch:
             # live state into the carry slot (no-op when the previous epoch
             # used this same graph; needed across pattern/mode switches)
             g.obs_full[steps].copy_(self._obs)
         g.replay()
         self._obs = g.obs_full[steps]
-        env.state = self._obs
-        return g.obs_full[:steps], g.act_buf, g.rew_buf, g.final_tensors()
-
-    # ------------------------------------------------------------------
-    def _sample_graphed_pendulum(self, policy, steps: int, cuts: Tuple[int, ...],
-                                 reset_epoch: bool):
-        """DevicePendulumEnv: the carry between epochs is the env's own fp64
-        `state`, which the kernels read and write in place; the observation
-        carry is derived from it, so nothing is copied in or out here."""
-        from rl_replicas_amd.ops import fused_rollout
-
-        env = self.env
-        if self._graph_ctr is None:
-            self._graph_ctr = fused_rollout.make_counter(env.device)
-        key = (steps, cuts, reset_epoch)
-        g = self._graphs.get(key)
-        if g is None:
-            g = fused_rollout.GraphedPendulumRollout(
-                policy, env, steps, cuts, reset_epoch, self._graph_ctr
-            )
-            self._graphs[key] = g
-        g.replay()
-        self._obs = g.obs_full[steps]
+        if not pendulum:
+            env.state = self._obs
         return g.obs_full[:steps], g.act_buf, g.rew_buf, g.final_tensors()
 
     # ------------------------------------------------------------------
@@ -189,13 +198,7 @@ class DeviceSampler(Sampler):
         N = self.num_envs
         device = self.env.device
 
-        seg_bounds: List[tuple] = []  # (start, end_exclusive, done)
-        start = 0
-        for c in cuts:
-            seg_bounds.append((start, c + 1, True))
-            start = c + 1
-        if start < steps:
-            seg_bounds.append((start, steps, False))
+        seg_bounds = segment_bounds(steps, cuts)
         n_segs = len(seg_bounds)
 
         # flat (instance-major) device views for the train pipeline
