@@ -96,7 +96,6 @@ __global__ void cartpole_env_step_kernel(double* state, int* elapsed,
 __global__ void cartpole_env_reset_kernel(double* state, int* elapsed, float* obs,
                                           int N, uint64_t seed, uint64_t offset,
                                           const unsigned long long* offset_ptr);
-size_t cartpole_rollout_fused_lds_bytes(const int* dims, int n_layers);
 void launch_cartpole_rollout_fused(const CartPoleRolloutArgs& a, hipStream_t stream);
 __global__ void pendulum_env_step_kernel(double* state, const float* actions,
                                          float* obs, float* final_obs,
@@ -106,14 +105,9 @@ __global__ void pendulum_env_step_kernel(double* state, const float* actions,
 __global__ void pendulum_env_reset_kernel(double* state, float* obs, int N,
                                           int draw, uint64_t seed, uint64_t offset,
                                           const unsigned long long* offset_ptr);
-size_t pendulum_rollout_fused_lds_bytes(const int* dims, int n_layers);
 void launch_pendulum_rollout_fused(const PendulumRolloutArgs& a, hipStream_t stream);
-bool pendulum_collect_fused_is_wide(const int* dims, int n_layers);
-size_t pendulum_collect_fused_lds_bytes(const int* dims, int n_layers);
 void launch_pendulum_collect_fused(const PendulumCollectArgs& a, int wide_threads,
                                    hipStream_t stream);
-bool eval_fused_is_wide(const int* dims, int n_layers);
-size_t eval_fused_lds_bytes(const int* dims, int n_layers);
 void launch_pendulum_eval_fused(const PendulumEvalArgs& a, int wide_threads,
                                 hipStream_t stream);
 void launch_cartpole_eval_fused(const CartPoleEvalArgs& a, hipStream_t stream);
@@ -139,7 +133,6 @@ __global__ void synthetic_env_reset_kernel(float* s_out, int total,
                                            const unsigned long long* offset_ptr);
 __global__ void counter_add_kernel(unsigned long long* ctr,
                                    unsigned long long delta);
-size_t ppo_rollout_fused_lds_bytes(const int* dims, int n_layers, int O, int A);
 void launch_ppo_rollout_fused(const RolloutFusedArgs& a, hipStream_t stream);
 __global__ void segmented_gae_kernel(const float* rewards, const float* values,
                                      const float* last_values, const int* offsets,
@@ -1116,6 +1109,52 @@ static void check_out(const torch::Tensor& t, torch::ScalarType dt, int64_t nume
               name, ": wrong device, dtype, layout or size");
 }
 
+// ---- checks shared by the persistent rollout / collect / evaluation bindings
+// the default per-workgroup dynamic-LDS limit (no opt-in attribute needed):
+// the budget of the CartPole and Pendulum rollout and the evaluation kernels
+#define DEFAULT_LDS_LIMIT (64 * 1024)
+
+// dynamic LDS of a persistent kernel with the observation tile + 2 activation
+// tiles beside the net (every one but the synthetic-env kernel)
+static size_t persistent_lds_bytes(const NetLayout& n) {
+  return (size_t)net_lds_floats(3, n.dims, n.L) * sizeof(float);
+}
+
+static size_t ppo_rollout_fused_lds_bytes(const NetLayout& n, int O, int A) {
+  return (size_t)rollout_fused_lds_floats(n.dims, n.L, O, A) * sizeof(float);
+}
+
+// an epoch's step count or an evaluation's horizon
+static int check_step_count(int64_t v, const char* name) {
+  TORCH_CHECK(v >= 1 && v <= (1 << 24), name, " out of range");
+  return (int)v;
+}
+
+static void check_net_device(const std::vector<torch::Tensor>& weights,
+                             const std::vector<torch::Tensor>& biases,
+                             const torch::Device& dev) {
+  for (const auto& t : weights)
+    TORCH_CHECK(t.device() == dev, "the net is on another device");
+  for (const auto& t : biases)
+    TORCH_CHECK(t.device() == dev, "the net is on another device");
+}
+
+// the lockstep cuts of an epoch of `steps` steps -> a.cut_step / a.n_cuts:
+// at most ROLLOUT_MAX_CUTS step indices, strictly ascending (what
+// lockstep_cuts of the samplers produces, and what makes slot j of the
+// cut-indexed outputs belong to cuts[j] alone)
+template <class Args>
+static void fill_cuts(Args& a, const std::vector<int64_t>& cuts, int64_t steps,
+                      const char* who) {
+  TORCH_CHECK(cuts.size() <= ROLLOUT_MAX_CUTS, who, ": too many cuts");
+  a.n_cuts = (int)cuts.size();
+  for (int c = 0; c < a.n_cuts; ++c) {
+    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < steps, "cut step out of range");
+    TORCH_CHECK(c == 0 || cuts[c] > cuts[c - 1], "cuts must be ascending");
+    a.cut_step[c] = (int)cuts[c];
+  }
+}
+
 // -> {obs, reward, done, final_obs}; state and elapsed are updated in place
 std::vector<torch::Tensor> cartpole_env_step(
     torch::Tensor state, torch::Tensor elapsed, torch::Tensor actions,
@@ -1766,7 +1805,7 @@ void counter_add_(torch::Tensor ctr, int64_t delta) {
 int64_t ppo_rollout_fused_lds_bytes_py(std::vector<int64_t> dims, int64_t O,
                                        int64_t A) {
   const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
-  return (int64_t)ppo_rollout_fused_lds_bytes(n.dims, n.L, (int)O, (int)A);
+  return (int64_t)ppo_rollout_fused_lds_bytes(n, (int)O, (int)A);
 }
 
 // whole-epoch rollout in one launch (rollout_fused_kernels.hip): writes
@@ -1811,17 +1850,12 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
   fill_net(a, net, weights, biases, acts);
   const int L = net.L;
   TORCH_CHECK(a.dims[L] == a.A, "policy head width must equal the action dim");
-  TORCH_CHECK(ppo_rollout_fused_lds_bytes(a.dims, L, a.O, a.A) <= MLP_LDS_BUDGET,
+  TORCH_CHECK(ppo_rollout_fused_lds_bytes(net, a.O, a.A) <= MLP_LDS_BUDGET,
               "ppo_rollout_fused: net + env image exceeds the LDS budget");
-  a.n_cuts = (int)cuts.size();
-  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "ppo_rollout_fused: too many cuts");
+  fill_cuts(a, cuts, a.steps, "ppo_rollout_fused");
   TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
                   cut_final.size(1) == a.N && cut_final.size(2) == a.O,
               "cut_final must be [n_cuts, N, O]");
-  for (int c = 0; c < a.n_cuts; ++c) {
-    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < a.steps, "cut step out of range");
-    a.cut_step[c] = (int)cuts[c];
-  }
   a.log_std = log_std.data_ptr<float>();
   a.envA = envA.data_ptr<float>();
   a.envB = envB.data_ptr<float>();
@@ -1839,14 +1873,10 @@ void ppo_rollout_fused(std::vector<torch::Tensor> weights,
   HIP_OK(hipGetLastError());
 }
 
-// LDS budget of the persistent CartPole kernel: the default per-workgroup
-// dynamic LDS limit (no opt-in attribute needed)
-#define CARTPOLE_ROLLOUT_MAX_LDS (64 * 1024)
-
 // dims = [4, hidden..., n_act] of the policy net
 int64_t cartpole_rollout_fused_lds_bytes_py(std::vector<int64_t> dims) {
   const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
-  return (int64_t)cartpole_rollout_fused_lds_bytes(n.dims, n.L);
+  return (int64_t)persistent_lds_bytes(n);
 }
 
 // whole-epoch CartPole rollout in one launch (cartpole_rollout_kernels.hip):
@@ -1862,7 +1892,6 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
                             torch::Tensor act_buf, torch::Tensor rew_buf,
                             torch::Tensor done_buf) {
   const NetLayout net = net_layout(4, weights, biases, acts, ROLLOUT_MAX_WIDTH);
-  const int L = net.L;
   CartPoleRolloutArgs a{};
   a.N = check_cartpole_carry(state, elapsed);
   check_f32_gpu(obs_full, "obs_full");
@@ -1876,7 +1905,7 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
   check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
   check_out(done_buf, torch::kUInt8, SN, "done_buf");
   fill_net(a, net, weights, biases, acts);
-  TORCH_CHECK(cartpole_rollout_fused_lds_bytes(a.dims, L) <= CARTPOLE_ROLLOUT_MAX_LDS,
+  TORCH_CHECK(persistent_lds_bytes(net) <= DEFAULT_LDS_LIMIT,
               "cartpole_rollout_fused: net image exceeds the LDS budget");
   a.state = state.data_ptr<double>();
   a.elapsed = elapsed.data_ptr<int>();
@@ -1897,13 +1926,13 @@ void cartpole_rollout_fused(std::vector<torch::Tensor> weights,
 // dims = [3, hidden..., 1] of the policy net
 int64_t pendulum_rollout_fused_lds_bytes_py(std::vector<int64_t> dims) {
   const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
-  return (int64_t)pendulum_rollout_fused_lds_bytes(n.dims, n.L);
+  return (int64_t)persistent_lds_bytes(n);
 }
 
 // whole-epoch Pendulum rollout in one launch (pendulum_rollout_kernels.hip):
 // writes obs_full[0..steps], act_buf, rew_buf, cut_final[j] for cuts[j] and
 // the env carry; reads the RNG counter, never advances it (counter_add_
-// follows).  Shares the CartPole kernel's LDS budget.
+// follows)
 void pendulum_rollout_fused(std::vector<torch::Tensor> weights,
                             std::vector<torch::Tensor> biases,
                             std::vector<int64_t> acts, torch::Tensor log_std,
@@ -1927,18 +1956,13 @@ void pendulum_rollout_fused(std::vector<torch::Tensor> weights,
   const int64_t SN = (int64_t)a.steps * a.N;
   check_out(act_buf, torch::kFloat32, SN, "act_buf");
   check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
-  a.n_cuts = (int)cuts.size();
-  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "pendulum_rollout_fused: too many cuts");
+  fill_cuts(a, cuts, a.steps, "pendulum_rollout_fused");
   check_f32_gpu(cut_final, "cut_final");
   TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
                   cut_final.size(1) == a.N && cut_final.size(2) == 3,
               "cut_final must be [n_cuts, N, 3]");
-  for (int c = 0; c < a.n_cuts; ++c) {
-    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < a.steps, "cut step out of range");
-    a.cut_step[c] = (int)cuts[c];
-  }
   fill_net(a, net, weights, biases, acts);
-  TORCH_CHECK(pendulum_rollout_fused_lds_bytes(a.dims, L) <= CARTPOLE_ROLLOUT_MAX_LDS,
+  TORCH_CHECK(persistent_lds_bytes(net) <= DEFAULT_LDS_LIMIT,
               "pendulum_rollout_fused: net image exceeds the LDS budget");
   a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
   a.log_std = log_std.data_ptr<float>();
@@ -2006,7 +2030,7 @@ static int epoch_segments(const std::vector<int64_t>& cuts, int64_t steps) {
 // dims = [3, hidden..., 1] of the actor
 int64_t pendulum_collect_fused_lds_bytes_py(std::vector<int64_t> dims) {
   const NetLayout n = net_layout(dims, MLP_MAX_WIDTH);
-  return (int64_t)pendulum_collect_fused_lds_bytes(n.dims, n.L);
+  return (int64_t)persistent_lds_bytes(n);
 }
 
 // whole-epoch Pendulum replay collection in one launch
@@ -2028,20 +2052,17 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
                             int64_t wide_threads) {
   PendulumCollectArgs a{};
   a.N = check_pendulum_carry(state);
-  TORCH_CHECK(steps >= 1 && steps <= (1 << 24), "steps out of range");
-  a.steps = (int)steps;
+  a.steps = check_step_count(steps, "steps");
   a.ring = check_ring(storage, write_dev, size_dev, (int64_t)a.N * steps,
                       state.device());
   TORCH_CHECK(mode == COLLECT_NOISED || mode == COLLECT_UNIFORM, "unknown mode");
   a.mode = (int)mode;
+  NetLayout net;  // no layers in uniform mode
   if (mode == COLLECT_NOISED) {
-    const NetLayout net = net_layout(3, weights, biases, acts, MLP_MAX_WIDTH);
+    net = net_layout(3, weights, biases, acts, MLP_MAX_WIDTH);
     TORCH_CHECK(net.dims[net.L] == 1,
                 "pendulum_collect_fused: the actor head must be 1 wide");
-    for (const auto& t : weights)
-      TORCH_CHECK(t.device() == state.device(), "actor is on another device");
-    for (const auto& t : biases)
-      TORCH_CHECK(t.device() == state.device(), "actor is on another device");
+    check_net_device(weights, biases, state.device());
     TORCH_CHECK(noise_scale >= 0.0 && limit >= 0.0,
                 "pendulum_collect_fused: noise_scale and limit must be >= 0");
     fill_net(a, net, weights, biases, acts);
@@ -2050,17 +2071,11 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
                 "pendulum_collect_fused: uniform mode takes no net");
     TORCH_CHECK(low <= high, "pendulum_collect_fused: low > high");
   }
-  TORCH_CHECK(pendulum_collect_fused_lds_bytes(a.dims, a.n_layers) <= MLP_LDS_BUDGET,
+  TORCH_CHECK(persistent_lds_bytes(net) <= MLP_LDS_BUDGET,
               "pendulum_collect_fused: net image exceeds the LDS budget");
   TORCH_CHECK(wide_threads == 256 || wide_threads == 1024,
               "pendulum_collect_fused: wide_threads must be 256 or 1024");
-  a.n_cuts = (int)cuts.size();
-  TORCH_CHECK(a.n_cuts <= ROLLOUT_MAX_CUTS, "pendulum_collect_fused: too many cuts");
-  for (int c = 0; c < a.n_cuts; ++c) {
-    TORCH_CHECK(cuts[c] >= 0 && cuts[c] < steps, "cut step out of range");
-    TORCH_CHECK(c == 0 || cuts[c] > cuts[c - 1], "cuts must be ascending");
-    a.cut_step[c] = (int)cuts[c];
-  }
+  fill_cuts(a, cuts, steps, "pendulum_collect_fused");
   a.n_segs = epoch_segments(cuts, steps);
   check_out(seg_returns, torch::kFloat32, (int64_t)a.N * a.n_segs, "seg_returns");
   check_out(last_obs, torch::kFloat32, (int64_t)a.N * 3, "last_obs");
@@ -2085,10 +2100,6 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
 // ---------------------------------------------------------------------------
 // GPU-resident policy evaluation (eval_kernels.hip)
 // ---------------------------------------------------------------------------
-// LDS budget of the persistent evaluation kernels: the default per-workgroup
-// dynamic LDS limit, like the CartPole and Pendulum rollout kernels
-#define EVAL_FUSED_MAX_LDS (64 * 1024)
-
 // the per-episode outputs of an evaluation: returns fp64 [N], lengths int32
 // [N], init_state fp64 [N, state_dim], all contiguous on one GPU.  -> N
 static int check_eval_outputs(const torch::Tensor& returns,
@@ -2124,25 +2135,16 @@ static void check_eval_counters(const torch::Tensor& ctr, const torch::Tensor& r
                 "ctr / reset_ctr must be 1-element int64 tensors on the outputs' device");
 }
 
-static void check_net_device(const std::vector<torch::Tensor>& weights,
-                             const std::vector<torch::Tensor>& biases,
-                             const torch::Device& dev) {
-  for (const auto& t : weights)
-    TORCH_CHECK(t.device() == dev, "the net is on another device");
-  for (const auto& t : biases)
-    TORCH_CHECK(t.device() == dev, "the net is on another device");
-}
-
 // dims = [3, hidden..., 1] of the policy net
 int64_t pendulum_eval_fused_lds_bytes_py(std::vector<int64_t> dims) {
   const NetLayout n = net_layout(dims, MLP_MAX_WIDTH);
-  return (int64_t)eval_fused_lds_bytes(n.dims, n.L);
+  return (int64_t)persistent_lds_bytes(n);
 }
 
 // dims = [4, hidden..., n_act] of the policy net
 int64_t cartpole_eval_fused_lds_bytes_py(std::vector<int64_t> dims) {
   const NetLayout n = net_layout(dims, ROLLOUT_MAX_WIDTH);
-  return (int64_t)eval_fused_lds_bytes(n.dims, n.L);
+  return (int64_t)persistent_lds_bytes(n);
 }
 
 // N whole Pendulum episodes of `horizon` steps in one launch
@@ -2161,8 +2163,7 @@ void pendulum_eval_fused(std::vector<torch::Tensor> weights,
   PendulumEvalArgs a{};
   a.N = check_eval_outputs(returns, lengths, init_state, 2);
   check_eval_counters(ctr, reset_ctr, returns.device());
-  TORCH_CHECK(horizon >= 1 && horizon <= (1 << 24), "horizon out of range");
-  a.horizon = (int)horizon;
+  a.horizon = check_step_count(horizon, "horizon");
   TORCH_CHECK(mode == EVAL_DETERMINISTIC || mode == EVAL_GAUSSIAN, "unknown mode");
   a.mode = (int)mode;
   const NetLayout net = net_layout(3, weights, biases, acts, MLP_MAX_WIDTH);
@@ -2176,7 +2177,7 @@ void pendulum_eval_fused(std::vector<torch::Tensor> weights,
     a.log_std = log_std->data_ptr<float>();
   }
   fill_net(a, net, weights, biases, acts);
-  TORCH_CHECK(eval_fused_lds_bytes(a.dims, a.n_layers) <= EVAL_FUSED_MAX_LDS,
+  TORCH_CHECK(persistent_lds_bytes(net) <= DEFAULT_LDS_LIMIT,
               "pendulum_eval_fused: net image exceeds the LDS budget");
   TORCH_CHECK(wide_threads == 256 || wide_threads == 1024,
               "pendulum_eval_fused: wide_threads must be 256 or 1024");
@@ -2203,12 +2204,11 @@ void cartpole_eval_fused(std::vector<torch::Tensor> weights,
   CartPoleEvalArgs a{};
   a.N = check_eval_outputs(returns, lengths, init_state, 4);
   check_eval_counters(ctr, reset_ctr, returns.device());
-  TORCH_CHECK(horizon >= 1 && horizon <= (1 << 24), "horizon out of range");
-  a.horizon = (int)horizon;
+  a.horizon = check_step_count(horizon, "horizon");
   const NetLayout net = net_layout(4, weights, biases, acts, ROLLOUT_MAX_WIDTH);
   check_net_device(weights, biases, returns.device());
   fill_net(a, net, weights, biases, acts);
-  TORCH_CHECK(eval_fused_lds_bytes(a.dims, a.n_layers) <= EVAL_FUSED_MAX_LDS,
+  TORCH_CHECK(persistent_lds_bytes(net) <= DEFAULT_LDS_LIMIT,
               "cartpole_eval_fused: net image exceeds the LDS budget");
   a.returns = returns.data_ptr<double>();
   a.lengths = lengths.data_ptr<int>();
@@ -2334,7 +2334,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dynamic LDS of pendulum_eval_fused for a net [3, ..., 1]");
   m.def("pendulum_eval_fused_limits",
         []() {
-          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH, EVAL_FUSED_MAX_LDS};
+          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH, DEFAULT_LDS_LIMIT};
         },
         "(max layers, max width, LDS budget in bytes) of pendulum_eval_fused");
   m.def("cartpole_eval_fused", &cartpole_eval_fused,
@@ -2348,7 +2348,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cartpole_eval_fused_limits",
         []() {
           return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
-                                      EVAL_FUSED_MAX_LDS};
+                                      DEFAULT_LDS_LIMIT};
         },
         "(max layers, max width, LDS budget in bytes) of cartpole_eval_fused");
   m.def("episode_reduce", &episode_reduce,
@@ -2397,7 +2397,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pendulum_rollout_fused_limits",
         []() {
           return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
-                                      ROLLOUT_MAX_CUTS, CARTPOLE_ROLLOUT_MAX_LDS};
+                                      ROLLOUT_MAX_CUTS, DEFAULT_LDS_LIMIT};
         },
         "(max layers, max width, max cuts, LDS budget in bytes) of "
         "pendulum_rollout_fused");
@@ -2424,7 +2424,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cartpole_rollout_fused_limits",
         []() {
           return std::vector<int64_t>{MLP_MAX_LAYERS, ROLLOUT_MAX_WIDTH,
-                                      CARTPOLE_ROLLOUT_MAX_LDS};
+                                      DEFAULT_LDS_LIMIT};
         },
         "(max layers, max width, LDS budget in bytes) of cartpole_rollout_fused");
   m.def("cartpole_env_step", &cartpole_env_step,

@@ -233,19 +233,48 @@ struct MLPBwdTwinArgs {
   const float* x;            // [B, dims[0]] of both nets
 };
 
-// persistent rollout kernel (rollout_fused_kernels.hip): one workgroup
-// carries ROLLOUT_ROWS env rows through all `steps` iterations of
-// forward -> Gaussian sample -> env transition.
+// The persistent kernels (rollout, collect, evaluation): one workgroup
+// carries ROLLOUT_ROWS env rows through a whole epoch or episode.
 #define ROLLOUT_ROWS 16
 #define ROLLOUT_MAX_WIDTH 64  // widest layer / obs dim (one wave per env row)
 #define ROLLOUT_LDSW (ROLLOUT_MAX_WIDTH + 4)  // LDS row stride of the 16-row tiles
 #define ROLLOUT_MAX_CUTS 16   // lockstep truncation cuts per captured epoch
-struct RolloutFusedArgs {
+// LDS row stride of the wide regime's 16-row activation tiles
+#define ROLLOUT_WIDE_LDSW (MLP_MAX_WIDTH + 4)
+
+// the net every persistent kernel's argument block starts with
+struct NetArgs {
   const float* w[MLP_MAX_LAYERS];
   const float* b[MLP_MAX_LAYERS];
   int dims[MLP_MAX_LAYERS + 1];
   int acts[MLP_MAX_LAYERS];
   int n_layers;
+};
+
+// The persistent kernels' weight regime, by mlp_forward's own rule: narrow
+// (every width <= MLP_NARROW_WIDTH) keeps the padded whole-net weight image
+// in LDS, wide reads the weights from global memory.
+__host__ __device__ inline bool net_is_wide(const int* dims, int n_layers) {
+  for (int l = 0; l <= n_layers; ++l)
+    if (dims[l] > MLP_NARROW_WIDTH) return true;
+  return false;
+}
+
+// LDS floats of a persistent kernel's net stage: `tiles` 16-row tiles;
+// narrow nets add the padded weight image ([out][in + 1] per layer) and the
+// biases.  Host sizing, launchers and *_lds_bytes all take it from here.
+__host__ __device__ inline long net_lds_floats(int tiles, const int* dims,
+                                               int n_layers) {
+  if (net_is_wide(dims, n_layers)) return (long)tiles * ROLLOUT_ROWS * ROLLOUT_WIDE_LDSW;
+  long n = (long)tiles * ROLLOUT_ROWS * ROLLOUT_LDSW;
+  for (int l = 0; l < n_layers; ++l) n += dims[l + 1] * (dims[l] + 1) + dims[l + 1];
+  return n;
+}
+
+// persistent rollout kernel (rollout_fused_kernels.hip): one workgroup
+// carries ROLLOUT_ROWS env rows through all `steps` iterations of
+// forward -> Gaussian sample -> synthetic env transition.
+struct RolloutFusedArgs : NetArgs {
   const float* log_std;  // [A]
   const float* envA;     // [O, O]
   const float* envB;     // [A, O]
@@ -255,7 +284,7 @@ struct RolloutFusedArgs {
   float* rew_buf;        // [steps, N]
   float* cut_final;      // [n_cuts, N, O] pre-reset successors, cut order
   const unsigned long long* ctr;  // device RNG counter (read once)
-  int cut_step[ROLLOUT_MAX_CUTS];
+  int cut_step[ROLLOUT_MAX_CUTS];  // ascending
   int n_cuts;
   int N, O, A, steps;
   int start_with_reset;  // 1: Philox reset; 0: continue from the carry slot
@@ -263,15 +292,17 @@ struct RolloutFusedArgs {
   uint64_t policy_seed, env_seed;
 };
 
+// its LDS floats: 2 state tiles (step ping-pong) + 2 activation tiles + 1
+// action tile and the net, then log_std and env A/B/w
+__host__ __device__ inline long rollout_fused_lds_floats(const int* dims, int n_layers,
+                                                         int O, int A) {
+  return net_lds_floats(5, dims, n_layers) + A + O * O + A * O + O;
+}
+
 // persistent CartPole rollout kernel (cartpole_rollout_kernels.hip): one
 // workgroup carries ROLLOUT_ROWS instances through all `steps` iterations
 // of forward -> categorical sample -> Euler step / termination / autoreset.
-struct CartPoleRolloutArgs {
-  const float* w[MLP_MAX_LAYERS];
-  const float* b[MLP_MAX_LAYERS];
-  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 4 (obs), dims[L] == n_act
-  int acts[MLP_MAX_LAYERS];
-  int n_layers;
+struct CartPoleRolloutArgs : NetArgs {  // dims[0] == 4 (obs), dims[L] == n_act
   double* state;           // [N, 4] env carry (read unless start_with_reset)
   int* elapsed;            // [N]    env carry
   float* obs_full;         // [steps + 1, N, 4]
@@ -288,12 +319,7 @@ struct CartPoleRolloutArgs {
 // persistent Pendulum rollout kernel (pendulum_rollout_kernels.hip): one
 // workgroup carries ROLLOUT_ROWS instances through all `steps` iterations
 // of forward -> Gaussian sample -> transition / lockstep autoreset.
-struct PendulumRolloutArgs {
-  const float* w[MLP_MAX_LAYERS];
-  const float* b[MLP_MAX_LAYERS];
-  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
-  int acts[MLP_MAX_LAYERS];
-  int n_layers;
+struct PendulumRolloutArgs : NetArgs {  // dims[0] == 3 (obs), dims[L] == 1 (torque)
   const float* log_std;    // [1]
   double* state;           // [N, 2] env carry (read unless start_with_reset)
   float* obs_full;         // [steps + 1, N, 3]
@@ -327,14 +353,8 @@ struct ReplayRing {
 // behaviour action -> transition / lockstep autoreset -> ring write.
 #define COLLECT_NOISED 0   // actor forward + clipped Gaussian noise
 #define COLLECT_UNIFORM 1  // uniform in [low, high]; no net is read
-// LDS row stride of the wide regime's 16-row activation tiles
-#define COLLECT_WIDE_LDSW (MLP_MAX_WIDTH + 4)
-struct PendulumCollectArgs {
-  const float* w[MLP_MAX_LAYERS];
-  const float* b[MLP_MAX_LAYERS];
-  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
-  int acts[MLP_MAX_LAYERS];
-  int n_layers;                  // 0 in uniform mode
+// dims[0] == 3 (obs), dims[L] == 1 (torque); n_layers == 0 in uniform mode
+struct PendulumCollectArgs : NetArgs {
   double* state;           // [N, 2] env carry (read unless start_with_reset)
   ReplayRing ring;
   float* seg_returns;      // [N, n_segs] per-row segment reward sums
@@ -355,12 +375,7 @@ struct PendulumCollectArgs {
 // the per-episode return, length and init state.
 #define EVAL_DETERMINISTIC 0  // action = the net's output (DeterministicPolicy)
 #define EVAL_GAUSSIAN 1       // action = mean + exp(log_std) * z
-struct PendulumEvalArgs {
-  const float* w[MLP_MAX_LAYERS];
-  const float* b[MLP_MAX_LAYERS];
-  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 3 (obs), dims[L] == 1 (torque)
-  int acts[MLP_MAX_LAYERS];
-  int n_layers;
+struct PendulumEvalArgs : NetArgs {  // dims[0] == 3 (obs), dims[L] == 1 (torque)
   const float* log_std;    // [1]; Gaussian mode only
   double* returns;         // [N] fp32 step rewards summed in step order
   int* lengths;            // [N] == horizon
@@ -372,12 +387,7 @@ struct PendulumEvalArgs {
   uint64_t policy_seed, env_seed;
 };
 
-struct CartPoleEvalArgs {
-  const float* w[MLP_MAX_LAYERS];
-  const float* b[MLP_MAX_LAYERS];
-  int dims[MLP_MAX_LAYERS + 1];  // dims[0] == 4 (obs), dims[L] == n_act
-  int acts[MLP_MAX_LAYERS];
-  int n_layers;
+struct CartPoleEvalArgs : NetArgs {  // dims[0] == 4 (obs), dims[L] == n_act
   double* returns;         // [N] == length (reward 1 per step)
   int* lengths;            // [N] in [1, horizon]
   double* init_state;      // [N, 4]

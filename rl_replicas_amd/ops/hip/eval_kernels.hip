@@ -22,97 +22,21 @@
 // Weight regimes are those of pendulum_collect_kernels.hip: narrow (every
 // width <= MLP_NARROW_WIDTH) keeps the padded whole-net weight image in LDS,
 // wide (Pendulum only, up to MLP_MAX_WIDTH) reads weights from global memory.
+// LDS: the observation tile + 2 activation tiles and the net (net_lds_floats,
+// common.h).
 //
 // Results are byte-identical to the multi-kernel body (env reset, then
 // mlp_forward -> [gaussian_sample | categorical_sample] -> env step per
-// step, then episode_reduce): the per-row arithmetic is the shared code of
-// rollout_steps.h and every Philox draw uses the same (seed, offset, row).
+// step, then episode_reduce): the net stage and the per-row arithmetic are
+// the shared code of rollout_steps.h and every Philox draw uses the same
+// (seed, offset, row).
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
 
-__host__ __device__ inline bool eval_is_wide(const int* dims, int n_layers) {
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] > MLP_NARROW_WIDTH) return true;
-  return false;
-}
-
-// LDS image (floats): the observation tile + 2 activation tiles; narrow
-// nets add the padded whole-net weight image ([out][in + 1] per layer) and
-// the biases
-__host__ __device__ inline long eval_lds_floats(const int* dims, int n_layers) {
-  if (eval_is_wide(dims, n_layers)) return 3L * ROLLOUT_ROWS * COLLECT_WIDE_LDSW;
-  long n = 3L * ROLLOUT_ROWS * ROLLOUT_LDSW;
-  for (int l = 0; l < n_layers; ++l) n += dims[l + 1] * (dims[l] + 1) + dims[l + 1];
-  return n;
-}
-
-// prologue of both kernels: (narrow) weights and biases -> LDS, the
-// observation tile zeroed.  Returns the LDS bias image (narrow) or nullptr.
-template <class Args, int NT, int LDSW, bool WIDE>
-DEV_INLINE const float* eval_stage_net(const Args& a, float* st, float* wl, int tid) {
-  const float* bl = nullptr;
-  if constexpr (!WIDE) {
-    int woff = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const int in_d = a.dims[l], out_d = a.dims[l + 1];
-      for (int idx = tid; idx < out_d * in_d; idx += NT) {
-        const int r = idx / in_d, c = idx % in_d;
-        wl[woff + r * (in_d + 1) + c] = a.w[l][idx];
-      }
-      woff += out_d * (in_d + 1);
-    }
-    float* const blw = wl + woff;
-    int boff = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      for (int idx = tid; idx < a.dims[l + 1]; idx += NT) blw[boff + idx] = a.b[l][idx];
-      boff += a.dims[l + 1];
-    }
-    bl = blw;
-  }
-  for (int idx = tid; idx < ROLLOUT_ROWS * LDSW; idx += NT) st[idx] = 0.f;
-  return bl;
-}
-
-// the net's forward on the LDS-resident observation tile; every thread of
-// the workgroup calls it (it ends each layer with a barrier).  Returns the
-// output tile [ROWS][LDSW], which never reaches HBM.
-template <class Args, int NT, int LDSW, bool WIDE>
-DEV_INLINE const float* eval_forward(const Args& a, const float* st, float* buf0,
-                                     float* buf1, const float* wl, const float* bl,
-                                     int wave, int lane) {
-  constexpr int NW = NT / 64;
-  const int i16 = lane & 15;
-  const int k4 = lane >> 4;
-  const float* buf_in = st;
-  int wo = 0, bo = 0;
-  for (int l = 0; l < a.n_layers; ++l) {
-    const int in_d = a.dims[l], out_d = a.dims[l + 1];
-    float* const buf_out = (l & 1) ? buf1 : buf0;
-    for (int jt = wave * 16; jt < out_d; jt += 16 * NW) {
-      const int j = jt + i16;
-      const bool jok = j < out_d;
-      if constexpr (WIDE) {
-        const f32x4 acc = mlp_fwd_tile_wide<LDSW>(buf_in, a.w[l] + (long)j * in_d,
-                                                  in_d, i16, k4, jok);
-        mlp_fwd_tile_epilogue<LDSW>(acc, a.b[l], a.acts[l], j, jok, 0, lane, buf_out);
-      } else {
-        const f32x4 acc = mlp_fwd_tile_lds<LDSW, false>(buf_in, wl + wo, in_d + 1,
-                                                        in_d, i16, k4, j, jok);
-        mlp_fwd_tile_epilogue<LDSW>(acc, bl + bo, a.acts[l], j, jok, 0, lane, buf_out);
-      }
-    }
-    __syncthreads();
-    buf_in = buf_out;
-    wo += out_d * (in_d + 1);
-    bo += out_d;
-  }
-  return buf_in;
-}
-
 template <int NT, bool WIDE>
 __global__ __launch_bounds__(NT) void pendulum_eval_fused_f32(PendulumEvalArgs a) {
-  constexpr int LDSW = WIDE ? COLLECT_WIDE_LDSW : ROLLOUT_LDSW;
+  constexpr int LDSW = WIDE ? ROLLOUT_WIDE_LDSW : ROLLOUT_LDSW;
   constexpr int ROWS = ROLLOUT_ROWS;
   extern __shared__ float smem[];
   float* const st = smem;
@@ -128,7 +52,8 @@ __global__ __launch_bounds__(NT) void pendulum_eval_fused_f32(PendulumEvalArgs a
   const uint64_t ctr = *a.ctr;
   const uint64_t reset_ctr = *a.reset_ctr;
 
-  const float* const bl = eval_stage_net<PendulumEvalArgs, NT, LDSW, WIDE>(a, st, wl, tid);
+  const NetStage net = net_stage<NT, WIDE>(a, wl, tid);
+  for (int idx = tid; idx < ROWS * LDSW; idx += NT) st[idx] = 0.f;
   __syncthreads();
 
   // thread r < 16 owns episode row0 + r: fp64 state in registers from the
@@ -150,7 +75,7 @@ __global__ __launch_bounds__(NT) void pendulum_eval_fused_f32(PendulumEvalArgs a
 
   for (int t = 0; t < horizon; ++t) {
     const float* const mean =
-        eval_forward<PendulumEvalArgs, NT, LDSW, WIDE>(a, st, buf0, buf1, wl, bl, wave, lane);
+        net_forward<NT, LDSW, WIDE>(a, st, buf0, buf1, wl, net.bl, wave, lane);
 
     // ---- action + env transition: thread r on its own row --------------
     if (owner) {
@@ -193,7 +118,8 @@ __global__ __launch_bounds__(NT) void cartpole_eval_fused_f32(CartPoleEvalArgs a
   const uint64_t ctr = *a.ctr;
   const uint64_t reset_ctr = *a.reset_ctr;
 
-  const float* const bl = eval_stage_net<CartPoleEvalArgs, NT, LDSW, false>(a, st, wl, tid);
+  const NetStage net = net_stage<NT, false>(a, wl, tid);
+  for (int idx = tid; idx < ROWS * LDSW; idx += NT) st[idx] = 0.f;
   __syncthreads();
 
   // thread r < 16 owns episode row0 + r: fp64 state, return and length in
@@ -216,7 +142,7 @@ __global__ __launch_bounds__(NT) void cartpole_eval_fused_f32(CartPoleEvalArgs a
 
   for (int t = 0; t < horizon; ++t) {
     const float* const logits =
-        eval_forward<CartPoleEvalArgs, NT, LDSW, false>(a, st, buf0, buf1, wl, bl, wave, lane);
+        net_forward<NT, LDSW, false>(a, st, buf0, buf1, wl, net.bl, wave, lane);
 
     // ---- sample + env transition: thread r on its own live row ---------
     // a finished row samples nothing, steps nothing and adds nothing; its
@@ -263,22 +189,14 @@ __global__ __launch_bounds__(256) void episode_reduce_kernel(
   }
 }
 
-bool eval_fused_is_wide(const int* dims, int n_layers) {
-  return eval_is_wide(dims, n_layers);
-}
-
-size_t eval_fused_lds_bytes(const int* dims, int n_layers) {
-  return (size_t)eval_lds_floats(dims, n_layers) * sizeof(float);
-}
-
 // Narrow: 4 waves, one 16-column tile each at width 64.  Wide: `wide_threads`
 // is 256 (each wave loops over four tiles of a 256-wide layer) or 1024 (one
 // tile per wave); the caller has checked it.
 void launch_pendulum_eval_fused(const PendulumEvalArgs& a, int wide_threads,
                                 hipStream_t stream) {
   const dim3 g((a.N + ROLLOUT_ROWS - 1) / ROLLOUT_ROWS);
-  const size_t lds = eval_fused_lds_bytes(a.dims, a.n_layers);
-  if (!eval_is_wide(a.dims, a.n_layers))
+  const size_t lds = net_lds_floats(3, a.dims, a.n_layers) * sizeof(float);
+  if (!net_is_wide(a.dims, a.n_layers))
     hipLaunchKernelGGL((pendulum_eval_fused_f32<256, false>), g, dim3(256), lds, stream, a);
   else if (wide_threads == 1024)
     hipLaunchKernelGGL((pendulum_eval_fused_f32<1024, true>), g, dim3(1024), lds, stream, a);
@@ -289,6 +207,6 @@ void launch_pendulum_eval_fused(const PendulumEvalArgs& a, int wide_threads,
 // narrow only (the caller has checked every width)
 void launch_cartpole_eval_fused(const CartPoleEvalArgs& a, hipStream_t stream) {
   const dim3 g((a.N + ROLLOUT_ROWS - 1) / ROLLOUT_ROWS);
-  const size_t lds = eval_fused_lds_bytes(a.dims, a.n_layers);
+  const size_t lds = net_lds_floats(3, a.dims, a.n_layers) * sizeof(float);
   hipLaunchKernelGGL((cartpole_eval_fused_f32<256>), g, dim3(256), lds, stream, a);
 }

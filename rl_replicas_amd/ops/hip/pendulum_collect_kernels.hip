@@ -14,7 +14,9 @@
 // instance-major order ReplayBuffer._add_flat_tensors produces, so no
 // staging buffer and no second copy exist.
 //
-// Two weight regimes, chosen on the host by mlp_forward's own rule:
+// Two weight regimes, chosen on the host by mlp_forward's own rule
+// (net_is_wide, common.h; the stage itself is net_stage / net_forward of
+// rollout_steps.h, LDS sized by net_lds_floats with 3 tiles):
 //   narrow (every width <= MLP_NARROW_WIDTH): the padded whole-net weight
 //          image in LDS, tiles from mlp_fwd_tile_lds;
 //   wide   (up to MLP_MAX_WIDTH): activations ping-pong between two
@@ -24,36 +26,16 @@
 //
 // Results are byte-identical to the multi-kernel body (mlp_forward ->
 // gaussian_sample | uniform_sample -> pendulum_env_step, then
-// replay_scatter): the per-row arithmetic is the shared code of
+// replay_scatter): the net stage and the per-row arithmetic are the shared code of
 // rollout_steps.h and every Philox draw uses the same (seed, offset, row).
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
 
-__host__ __device__ inline bool pendulum_collect_is_wide(const int* dims,
-                                                         int n_layers) {
-  for (int l = 0; l <= n_layers; ++l)
-    if (dims[l] > MLP_NARROW_WIDTH) return true;
-  return false;
-}
-
-// LDS image (floats): the observation tile + 2 activation tiles; narrow
-// nets add the padded whole-net weight image ([out][in + 1] per layer) and
-// the biases
-__host__ __device__ inline long pendulum_collect_lds_floats(const int* dims,
-                                                            int n_layers) {
-  if (pendulum_collect_is_wide(dims, n_layers))
-    return 3L * ROLLOUT_ROWS * COLLECT_WIDE_LDSW;
-  long n = 3L * ROLLOUT_ROWS * ROLLOUT_LDSW;
-  for (int l = 0; l < n_layers; ++l) n += dims[l + 1] * (dims[l] + 1) + dims[l + 1];
-  return n;
-}
-
 template <int NT, bool WIDE>
 __global__ __launch_bounds__(NT) void pendulum_collect_fused_f32(PendulumCollectArgs a) {
-  constexpr int LDSW = WIDE ? COLLECT_WIDE_LDSW : ROLLOUT_LDSW;
+  constexpr int LDSW = WIDE ? ROLLOUT_WIDE_LDSW : ROLLOUT_LDSW;
   constexpr int ROWS = ROLLOUT_ROWS;
-  constexpr int NW = NT / 64;
   extern __shared__ float smem[];
   float* const st = smem;
   float* const buf0 = st + ROWS * LDSW;
@@ -71,25 +53,7 @@ __global__ __launch_bounds__(NT) void pendulum_collect_fused_f32(PendulumCollect
   const unsigned long long write = (unsigned long long)*a.ring.write % cap;
 
   // ---- prologue: (narrow) weights, biases -> LDS ------------------------
-  const float* bl = nullptr;
-  if constexpr (!WIDE) {
-    int woff = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const int in_d = a.dims[l], out_d = a.dims[l + 1];
-      for (int idx = tid; idx < out_d * in_d; idx += NT) {
-        const int r = idx / in_d, c = idx % in_d;
-        wl[woff + r * (in_d + 1) + c] = a.w[l][idx];
-      }
-      woff += out_d * (in_d + 1);
-    }
-    float* const blw = wl + woff;
-    int boff = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      for (int idx = tid; idx < a.dims[l + 1]; idx += NT) blw[boff + idx] = a.b[l][idx];
-      boff += a.dims[l + 1];
-    }
-    bl = blw;
-  }
+  const NetStage net = net_stage<NT, WIDE>(a, wl, tid);
   for (int idx = tid; idx < ROWS * LDSW; idx += NT) st[idx] = 0.f;
   __syncthreads();
 
@@ -112,40 +76,15 @@ __global__ __launch_bounds__(NT) void pendulum_collect_fused_f32(PendulumCollect
   }
   __syncthreads();
 
-  const int i16 = lane & 15;
-  const int k4 = lane >> 4;
   float seg_acc = 0.f;  // this row's reward sum of the running segment
   for (int t = 0; t < steps; ++t) {
     // ---- actor forward on the LDS-resident observation tile ------------
-    const float* buf_in = st;
-    int wo = 0, bo = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const int in_d = a.dims[l], out_d = a.dims[l + 1];
-      float* const buf_out = (l & 1) ? buf1 : buf0;
-      for (int jt = wave * 16; jt < out_d; jt += 16 * NW) {
-        const int j = jt + i16;
-        const bool jok = j < out_d;
-        if constexpr (WIDE) {
-          const f32x4 acc = mlp_fwd_tile_wide<LDSW>(
-              buf_in, a.w[l] + (long)j * in_d, in_d, i16, k4, jok);
-          mlp_fwd_tile_epilogue<LDSW>(acc, a.b[l], a.acts[l], j, jok, 0, lane, buf_out);
-        } else {
-          const f32x4 acc = mlp_fwd_tile_lds<LDSW, false>(buf_in, wl + wo, in_d + 1,
-                                                          in_d, i16, k4, j, jok);
-          mlp_fwd_tile_epilogue<LDSW>(acc, bl + bo, a.acts[l], j, jok, 0, lane, buf_out);
-        }
-      }
-      __syncthreads();
-      buf_in = buf_out;
-      wo += out_d * (in_d + 1);
-      bo += out_d;
-    }
-    const float* const mean = buf_in;  // [ROWS][LDSW], column 0; never in HBM
+    // column 0 of the output tile (unread in uniform mode: no layers)
+    const float* const mean =
+        net_forward<NT, LDSW, WIDE>(a, st, buf0, buf1, wl, net.bl, wave, lane);
 
     // lockstep truncation: the host's cut list says whether step t resets
-    int cslot = -1;
-    for (int c = 0; c < a.n_cuts; ++c)
-      if (a.cut_step[c] == t) cslot = c;
+    const int cslot = cut_slot(a.cut_step, a.n_cuts, t);
     const int do_reset = cslot >= 0;
 
     // ---- action + env transition + ring write: thread r on its own row --
@@ -191,22 +130,14 @@ __global__ __launch_bounds__(NT) void pendulum_collect_fused_f32(PendulumCollect
   }
 }
 
-bool pendulum_collect_fused_is_wide(const int* dims, int n_layers) {
-  return pendulum_collect_is_wide(dims, n_layers);
-}
-
-size_t pendulum_collect_fused_lds_bytes(const int* dims, int n_layers) {
-  return (size_t)pendulum_collect_lds_floats(dims, n_layers) * sizeof(float);
-}
-
 // Narrow: 4 waves, one 16-column tile each at width 64.  Wide: `wide_threads`
 // is 256 (each wave loops over four tiles of a 256-wide layer) or 1024 (one
 // tile per wave); the caller has checked it.
 void launch_pendulum_collect_fused(const PendulumCollectArgs& a, int wide_threads,
                                    hipStream_t stream) {
   const dim3 g((a.N + ROLLOUT_ROWS - 1) / ROLLOUT_ROWS);
-  const size_t lds = pendulum_collect_fused_lds_bytes(a.dims, a.n_layers);
-  if (!pendulum_collect_is_wide(a.dims, a.n_layers))
+  const size_t lds = net_lds_floats(3, a.dims, a.n_layers) * sizeof(float);
+  if (!net_is_wide(a.dims, a.n_layers))
     hipLaunchKernelGGL((pendulum_collect_fused_f32<256, false>), g, dim3(256), lds,
                        stream, a);
   else if (wide_threads == 1024)

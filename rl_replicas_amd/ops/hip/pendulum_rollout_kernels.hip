@@ -9,27 +9,18 @@
 // synchronisation is the workgroup barrier.
 //
 // Results are byte-identical to the multi-kernel body (mlp_forward ->
-// gaussian_sample -> pendulum_env_step): the per-row arithmetic is the
-// shared code of rollout_steps.h and every Philox draw uses the same
-// (seed, offset, row).
+// gaussian_sample -> pendulum_env_step): the net stage and the per-row
+// arithmetic are the shared code of rollout_steps.h and every Philox draw
+// uses the same (seed, offset, row).  LDS: the observation tile + 2
+// activation tiles and the net (net_lds_floats, common.h).
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
-
-// LDS image (floats): the observation tile + 2 activation tiles, the padded
-// whole-net weight image ([out][in + 1] per layer), biases.
-__host__ __device__ inline int pendulum_rollout_lds_floats(const int* dims,
-                                                           int n_layers) {
-  int n = 3 * ROLLOUT_ROWS * ROLLOUT_LDSW;
-  for (int l = 0; l < n_layers; ++l) n += dims[l + 1] * (dims[l] + 1) + dims[l + 1];
-  return n;
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void pendulum_rollout_fused_f32(PendulumRolloutArgs a) {
   constexpr int LDSW = ROLLOUT_LDSW;
   constexpr int ROWS = ROLLOUT_ROWS;
-  constexpr int NW = NT / 64;
   extern __shared__ float smem[];
   float* const st = smem;
   float* const buf0 = st + ROWS * LDSW;
@@ -44,21 +35,7 @@ __global__ __launch_bounds__(NT) void pendulum_rollout_fused_f32(PendulumRollout
   const uint64_t ctr = *a.ctr;  // read once; the bump is a later graph node
 
   // ---- prologue: weights, biases -> LDS ---------------------------------
-  int woff = 0;
-  for (int l = 0; l < a.n_layers; ++l) {
-    const int in_d = a.dims[l], out_d = a.dims[l + 1];
-    for (int idx = tid; idx < out_d * in_d; idx += NT) {
-      const int r = idx / in_d, c = idx % in_d;
-      wl[woff + r * (in_d + 1) + c] = a.w[l][idx];
-    }
-    woff += out_d * (in_d + 1);
-  }
-  float* const bl = wl + woff;
-  int boff = 0;
-  for (int l = 0; l < a.n_layers; ++l) {
-    for (int idx = tid; idx < a.dims[l + 1]; idx += NT) bl[boff + idx] = a.b[l][idx];
-    boff += a.dims[l + 1];
-  }
+  const NetStage net = net_stage<NT, false>(a, wl, tid);
   for (int idx = tid; idx < ROWS * LDSW; idx += NT) st[idx] = 0.f;
   __syncthreads();
 
@@ -84,33 +61,14 @@ __global__ __launch_bounds__(NT) void pendulum_rollout_fused_f32(PendulumRollout
   }
   __syncthreads();
 
-  const int i16 = lane & 15;
-  const int k4 = lane >> 4;
   for (int t = 0; t < steps; ++t) {
     // ---- policy forward on the LDS-resident observation tile -----------
-    const float* buf_in = st;
-    int wo = 0, bo = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const int in_d = a.dims[l], out_d = a.dims[l + 1];
-      float* const buf_out = (l & 1) ? buf1 : buf0;
-      for (int jt = wave * 16; jt < out_d; jt += 16 * NW) {
-        const int j = jt + i16;
-        const bool jok = j < out_d;
-        const f32x4 acc = mlp_fwd_tile_lds<LDSW, false>(buf_in, wl + wo, in_d + 1,
-                                                        in_d, i16, k4, j, jok);
-        mlp_fwd_tile_epilogue<LDSW>(acc, bl + bo, a.acts[l], j, jok, 0, lane, buf_out);
-      }
-      __syncthreads();
-      buf_in = buf_out;
-      wo += out_d * (in_d + 1);
-      bo += out_d;
-    }
-    const float* const mean = buf_in;  // [ROWS][LDSW], column 0; never in HBM
+    // column 0 of the output tile
+    const float* const mean =
+        net_forward<NT, LDSW, false>(a, st, buf0, buf1, wl, net.bl, wave, lane);
 
     // lockstep truncation: the host's cut list says whether step t resets
-    int slot = -1;
-    for (int c = 0; c < a.n_cuts; ++c)
-      if (a.cut_step[c] == t) slot = c;
+    const int slot = cut_slot(a.cut_step, a.n_cuts, t);
     const int do_reset = slot >= 0;
 
     // ---- sample + env transition: thread r on its own row --------------
@@ -147,13 +105,9 @@ __global__ __launch_bounds__(NT) void pendulum_rollout_fused_f32(PendulumRollout
   }
 }
 
-size_t pendulum_rollout_fused_lds_bytes(const int* dims, int n_layers) {
-  return (size_t)pendulum_rollout_lds_floats(dims, n_layers) * sizeof(float);
-}
-
 // 4 waves per workgroup: one 16-column output tile each at width 64
 void launch_pendulum_rollout_fused(const PendulumRolloutArgs& a, hipStream_t stream) {
   const dim3 g((a.N + ROLLOUT_ROWS - 1) / ROLLOUT_ROWS);
-  const size_t lds = pendulum_rollout_fused_lds_bytes(a.dims, a.n_layers);
+  const size_t lds = net_lds_floats(3, a.dims, a.n_layers) * sizeof(float);
   hipLaunchKernelGGL((pendulum_rollout_fused_f32<256>), g, dim3(256), lds, stream, a);
 }

@@ -10,24 +10,14 @@
 // the only synchronisation is the workgroup barrier.  Nothing here waits
 // on another workgroup.
 //
-// Results are byte-identical to the three-kernel path: the per-row
-// arithmetic is the shared code of rollout_steps.h, the env part keeps the
+// Results are byte-identical to the three-kernel path: the net stage and
+// the per-row arithmetic are the shared code of rollout_steps.h (sizing:
+// rollout_fused_lds_floats, common.h), the env part keeps the
 // one-wave-per-row lane mapping (same reduction tree), and every Philox
 // draw uses the same (seed, offset, element index).
 #include "common.h"
 #include "philox.h"
 #include "rollout_steps.h"
-
-// LDS image (floats): 2 state tiles (step ping-pong) + 2 activation tiles
-// + 1 action tile, the padded whole-net weight image ([out][in + 1] per
-// layer, as fused_mlp_fwd_f32_t stages it), biases, log_std, env A/B/w.
-__host__ __device__ inline int rollout_fused_lds_floats(const int* dims,
-                                                        int n_layers, int O,
-                                                        int A) {
-  int n = 5 * ROLLOUT_ROWS * ROLLOUT_LDSW;
-  for (int l = 0; l < n_layers; ++l) n += dims[l + 1] * (dims[l] + 1) + dims[l + 1];
-  return n + A + O * O + A * O + O;
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void ppo_rollout_fused_f32(RolloutFusedArgs a) {
@@ -50,22 +40,8 @@ __global__ __launch_bounds__(NT) void ppo_rollout_fused_f32(RolloutFusedArgs a) 
   const uint64_t ctr = *a.ctr;  // read once; the bump is a later graph node
 
   // ---- prologue: weights, biases, log_std, env matrices -> LDS ----------
-  int woff = 0;
-  for (int l = 0; l < a.n_layers; ++l) {
-    const int in_d = a.dims[l], out_d = a.dims[l + 1];
-    for (int idx = tid; idx < out_d * in_d; idx += NT) {
-      const int r = idx / in_d, c = idx % in_d;
-      wl[woff + r * (in_d + 1) + c] = a.w[l][idx];
-    }
-    woff += out_d * (in_d + 1);
-  }
-  float* const bl = wl + woff;
-  int boff = 0;
-  for (int l = 0; l < a.n_layers; ++l) {
-    for (int idx = tid; idx < a.dims[l + 1]; idx += NT) bl[boff + idx] = a.b[l][idx];
-    boff += a.dims[l + 1];
-  }
-  float* const lstd = bl + boff;
+  const NetStage net = net_stage<NT, false>(a, wl, tid);
+  float* const lstd = net.end;
   float* const eA = lstd + A;
   float* const eB = eA + O * O;
   float* const ew = eB + A * O;
@@ -94,31 +70,13 @@ __global__ __launch_bounds__(NT) void ppo_rollout_fused_f32(RolloutFusedArgs a) 
   }
   __syncthreads();
 
-  const int i16 = lane & 15;
-  const int k4 = lane >> 4;
   for (int t = 0; t < steps; ++t) {
     const float* const st = (t & 1) ? st1 : st0;
     float* const st_next = (t & 1) ? st0 : st1;
 
     // ---- policy forward on the LDS-resident state tile -----------------
-    const float* buf_in = st;
-    int wo = 0, bo = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-      const int in_d = a.dims[l], out_d = a.dims[l + 1];
-      float* const buf_out = (l & 1) ? buf1 : buf0;
-      for (int jt = wave * 16; jt < out_d; jt += 16 * NW) {
-        const int j = jt + i16;
-        const bool jok = j < out_d;
-        const f32x4 acc = mlp_fwd_tile_lds<LDSW, false>(buf_in, wl + wo, in_d + 1,
-                                                        in_d, i16, k4, j, jok);
-        mlp_fwd_tile_epilogue<LDSW>(acc, bl + bo, a.acts[l], j, jok, 0, lane, buf_out);
-      }
-      __syncthreads();
-      buf_in = buf_out;
-      wo += out_d * (in_d + 1);
-      bo += out_d;
-    }
-    const float* const mean = buf_in;  // [ROWS][LDSW], never written to HBM
+    const float* const mean =
+        net_forward<NT, LDSW, false>(a, st, buf0, buf1, wl, net.bl, wave, lane);
 
     // ---- action sample: a = mean + exp(log_std) * z --------------------
     float* const act_t = a.act_buf + (long)t * N * A;
@@ -137,9 +95,7 @@ __global__ __launch_bounds__(NT) void ppo_rollout_fused_f32(RolloutFusedArgs a) 
     __syncthreads();
 
     // ---- env transition: one wave per row ------------------------------
-    int slot = -1;
-    for (int c = 0; c < a.n_cuts; ++c)
-      if (a.cut_step[c] == t) slot = c;
+    const int slot = cut_slot(a.cut_step, a.n_cuts, t);
     const int do_reset = slot >= 0;
     float* const obs_next = a.obs_full + (long)(t + 1) * N * O;
     for (int r = wave; r < ROWS; r += NW) {
@@ -160,13 +116,9 @@ __global__ __launch_bounds__(NT) void ppo_rollout_fused_f32(RolloutFusedArgs a) 
   }
 }
 
-size_t ppo_rollout_fused_lds_bytes(const int* dims, int n_layers, int O, int A) {
-  return (size_t)rollout_fused_lds_floats(dims, n_layers, O, A) * sizeof(float);
-}
-
 // 16 waves per workgroup: one env row per wave in the transition part
 void launch_ppo_rollout_fused(const RolloutFusedArgs& a, hipStream_t stream) {
   const dim3 g((a.N + ROLLOUT_ROWS - 1) / ROLLOUT_ROWS);
-  const size_t lds = ppo_rollout_fused_lds_bytes(a.dims, a.n_layers, a.O, a.A);
+  const size_t lds = rollout_fused_lds_floats(a.dims, a.n_layers, a.O, a.A) * sizeof(float);
   hipLaunchKernelGGL((ppo_rollout_fused_f32<1024>), g, dim3(1024), lds, stream, a);
 }

@@ -1,12 +1,19 @@
 // Per-row arithmetic of one rollout step, shared by the stand-alone
-// kernels (fused_mlp_fwd_f32_t, gaussian_sample_kernel,
-// categorical_sample_kernel, synthetic_env_step_kernel,
-// cartpole_env_step_kernel, pendulum_env_step_kernel) and the persistent
-// rollout kernels (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip,
-// pendulum_rollout_kernels.hip).  Every caller
-// inlines the SAME expressions in the SAME order, so both routes produce
-// the same bytes; the operands may live in global memory or in LDS.
+// kernels (fused_mlp_fwd_f32_t, mlp_layer_fwd_wide_f32, the gaussian /
+// categorical / uniform sample kernels, the synthetic / cartpole / pendulum
+// env step and reset kernels, replay_scatter_kernel) and the persistent
+// kernels (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip,
+// pendulum_rollout_kernels.hip, pendulum_collect_kernels.hip,
+// eval_kernels.hip).  Every caller inlines the SAME expressions in the SAME
+// order, so both routes produce the same bytes; the operands may live in
+// global memory or in LDS.
+//
+// The persistent kernels also share their net stage from here: net_stage
+// (weight image -> LDS), net_forward (the per-step forward) and cut_slot.
+// It has ONE definition so that a fix cannot reach some of them only.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include "common.h"
 #include "philox.h"
 
@@ -62,7 +69,7 @@ DEV_INLINE void mlp_fwd_tile_epilogue(f32x4 acc, const float* B, int act, int j,
 // output column j from global memory.  Lane (i = lane & 15, k = lane >> 4).
 // The accumulation order is fixed: two chains over the 8-wide K blocks, the
 // single 4-block and the ragged tail on the first chain, then acc += acc2.
-// Shared by mlp_layer_fwd_wide_f32 and pendulum_collect_fused_f32.
+// Shared by mlp_layer_fwd_wide_f32 and net_forward's wide regime.
 template <int LDSW>
 DEV_INLINE f32x4 mlp_fwd_tile_wide(const float* xt, const float* wrow, int in_d,
                                    int i, int k, bool jok) {
@@ -98,6 +105,87 @@ DEV_INLINE f32x4 mlp_fwd_tile_wide(const float* xt, const float* wrow, int in_d,
   }
   acc[0] += acc2[0]; acc[1] += acc2[1]; acc[2] += acc2[2]; acc[3] += acc2[3];
   return acc;
+}
+
+// ---- the net stage of the persistent kernels ------------------------------
+// A workgroup of NT threads runs the net on a 16-row LDS tile every step.
+// Narrow nets (net_is_wide false) keep the padded weight image and the biases
+// in LDS from `wl` on, sized by net_lds_floats; wide nets read both from
+// global memory.
+
+// where net_stage left the biases, and the first free LDS float after them
+struct NetStage {
+  const float* bl;  // LDS bias image, layers back to back (nullptr when wide)
+  float* end;
+};
+
+// prologue: (narrow) weights [out][in + 1] per layer, then biases -> LDS at
+// wl.  The caller's barrier makes them visible.
+template <int NT, bool WIDE>
+DEV_INLINE NetStage net_stage(const NetArgs& a, float* wl, int tid) {
+  if constexpr (WIDE) return {nullptr, wl};
+  int woff = 0;
+  for (int l = 0; l < a.n_layers; ++l) {
+    const int in_d = a.dims[l], out_d = a.dims[l + 1];
+    for (int idx = tid; idx < out_d * in_d; idx += NT) {
+      const int r = idx / in_d, c = idx % in_d;
+      wl[woff + r * (in_d + 1) + c] = a.w[l][idx];
+    }
+    woff += out_d * (in_d + 1);
+  }
+  float* const bl = wl + woff;
+  int boff = 0;
+  for (int l = 0; l < a.n_layers; ++l) {
+    for (int idx = tid; idx < a.dims[l + 1]; idx += NT) bl[boff + idx] = a.b[l][idx];
+    boff += a.dims[l + 1];
+  }
+  return {bl, bl + boff};
+}
+
+// the net's forward on the LDS-resident tile st[ROWS][LDSW], activations
+// ping-ponging between buf0 and buf1; every thread of the workgroup calls it
+// (it ends each layer with a barrier).  Returns the output tile [ROWS][LDSW],
+// which never reaches HBM: buf0 or buf1 by the layer count, st without layers.
+template <int NT, int LDSW, bool WIDE>
+DEV_INLINE const float* net_forward(const NetArgs& a, const float* st, float* buf0,
+                                    float* buf1, const float* wl, const float* bl,
+                                    int wave, int lane) {
+  constexpr int NW = NT / 64;
+  const int i16 = lane & 15;
+  const int k4 = lane >> 4;
+  const float* buf_in = st;
+  int wo = 0, bo = 0;
+  for (int l = 0; l < a.n_layers; ++l) {
+    const int in_d = a.dims[l], out_d = a.dims[l + 1];
+    float* const buf_out = (l & 1) ? buf1 : buf0;
+    for (int jt = wave * 16; jt < out_d; jt += 16 * NW) {
+      const int j = jt + i16;
+      const bool jok = j < out_d;
+      if constexpr (WIDE) {
+        const f32x4 acc = mlp_fwd_tile_wide<LDSW>(buf_in, a.w[l] + (long)j * in_d,
+                                                  in_d, i16, k4, jok);
+        mlp_fwd_tile_epilogue<LDSW>(acc, a.b[l], a.acts[l], j, jok, 0, lane, buf_out);
+      } else {
+        const f32x4 acc = mlp_fwd_tile_lds<LDSW, false>(buf_in, wl + wo, in_d + 1,
+                                                        in_d, i16, k4, j, jok);
+        mlp_fwd_tile_epilogue<LDSW>(acc, bl + bo, a.acts[l], j, jok, 0, lane, buf_out);
+      }
+    }
+    __syncthreads();
+    buf_in = buf_out;
+    wo += out_d * (in_d + 1);
+    bo += out_d;
+  }
+  return buf_in;
+}
+
+// lockstep truncation: the slot of step t in the host's ascending cut list,
+// -1 when t is no cut
+DEV_INLINE int cut_slot(const int* cut_step, int n_cuts, int t) {
+  int slot = -1;
+  for (int c = 0; c < n_cuts; ++c)
+    if (cut_step[c] == t) slot = c;
+  return slot;
 }
 
 // one uniform action element in [low, high], keyed by (seed, offset, i)

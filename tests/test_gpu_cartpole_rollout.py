@@ -22,7 +22,10 @@ pytestmark = pytest.mark.gpu
 
 DEVICE = "cuda"
 NS = [5, 16, 37]
-NETS = {"bench": [4, 64, 32, 2], "awkward": [4, 7, 2]}
+NETS = {"bench": [4, 64, 32, 2], "awkward": [4, 7, 2],
+        # the layer-count ends of the shared forward: one layer (the output stays
+        # in the first activation buffer) and five (MLP_MAX_LAYERS), ragged
+        "one_layer": [4, 2], "five_layers": [4, 16, 24, 8, 40, 2]}
 STEPS = 6
 HORIZON = 4
 CTR_BASE = 1 << 40

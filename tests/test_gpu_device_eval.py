@@ -27,8 +27,14 @@ PENDULUM_CASES = [
     ("deterministic", [3, 7, 1]), ("deterministic", [3, 64, 32, 1]),
     ("deterministic", [3, 70, 256, 1]), ("deterministic", [3, 256, 256, 1]),
     ("gaussian", [3, 7, 1]), ("gaussian", [3, 64, 32, 1]),
+    # the layer-count ends of the shared forward: one layer (the output stays in
+    # the first activation buffer), five (MLP_MAX_LAYERS) ragged, and five wide
+    # with narrow layers in between
+    ("deterministic", [3, 1]), ("deterministic", [3, 16, 24, 8, 40, 1]),
+    ("deterministic", [3, 70, 8, 256, 12, 1]),
+    ("gaussian", [3, 1]), ("gaussian", [3, 16, 24, 8, 40, 1]),
 ]
-CARTPOLE_NETS = [[4, 7, 2], [4, 64, 32, 2]]
+CARTPOLE_NETS = [[4, 7, 2], [4, 64, 32, 2], [4, 2], [4, 16, 24, 8, 40, 2]]
 X_THRESHOLD = 2.4
 THETA_THRESHOLD = 12 * 2 * np.pi / 360
 

@@ -24,7 +24,10 @@ pytestmark = pytest.mark.gpu
 
 DEVICE = "cuda"
 NS = [5, 16, 37]
-NETS = {"bench": [3, 64, 32, 1], "awkward": [3, 7, 1]}
+NETS = {"bench": [3, 64, 32, 1], "awkward": [3, 7, 1],
+        # the layer-count ends of the shared forward: one layer (the output stays
+        # in the first activation buffer) and five (MLP_MAX_LAYERS), ragged
+        "one_layer": [3, 1], "five_layers": [3, 16, 24, 8, 40, 1]}
 STEPS = 6
 HORIZON = 4
 CTR_BASE = 1 << 40
@@ -447,3 +450,36 @@ def test_ddpg_epoch_on_the_eager_loop(tmp_path):
     assert env._elapsed == 5 and env._philox_offset == 6  # one reset, five steps
     for p in list(pnet.parameters()) + list(qnet.parameters()):
         assert torch.isfinite(p).all()
+
+
+def test_binding_refuses_cuts_that_do_not_ascend():
+    """pendulum_rollout_fused takes the cut list lockstep_cuts produces:
+    strictly ascending steps of the epoch.  Anything else is refused before
+    the launch, so slot j of cut_final belongs to cuts[j] alone."""
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.ops.fused_mlp import _extract_layers
+
+    ext = ops._load_extension()
+    n, steps = 5, 6
+    weights, biases, acts = _extract_layers(MLP(NETS["awkward"]).to(DEVICE))
+    log_std = torch.zeros(1, device=DEVICE)
+
+    def call(cuts):
+        obs_full = torch.full((steps + 1, n, 3), -777.0, device=DEVICE)
+        ext.pendulum_rollout_fused(
+            list(weights), list(biases), acts, log_std, 11, 12, list(cuts), True,
+            torch.full((1,), 1 << 40, dtype=torch.int64, device=DEVICE),
+            torch.zeros(n, 2, dtype=torch.float64, device=DEVICE), obs_full,
+            torch.zeros(steps, n, 1, device=DEVICE), torch.zeros(steps, n, device=DEVICE),
+            torch.zeros(2, n, 3, device=DEVICE))
+        torch.cuda.synchronize()
+        return obs_full
+
+    assert (call((1, 3)) != -777.0).all()
+    for cuts in ((3, 1), (2, 2)):  # unsorted, repeated
+        with pytest.raises(RuntimeError, match="ascending"):
+            call(cuts)
+    for cuts in ((6,), (-1,)):
+        with pytest.raises(RuntimeError, match="out of range"):
+            call(cuts)

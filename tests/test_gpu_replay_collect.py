@@ -10,7 +10,10 @@ N = 5 (less than one 16-row tile), 16 (exactly one), 37 (two tiles and a
 and the carried second one after steps 1 and 5.  Nets (ReLU, Tanh head):
 [3,64,32,1] and [3,7,1] narrow; [3,256,256,1] (the benchmark actor) and
 [3,70,256,1] wide, whose K = 3 has only the ragged tail, K = 70 8-blocks,
-the 4-block and a tail, K = 256 8-blocks only."""
+the 4-block and a tail, K = 256 8-blocks only.  The layer-count ends of the
+shared forward: [3,1] (one layer: the output stays in the first activation
+buffer), the ragged [3,16,24,8,40,1] (five, MLP_MAX_LAYERS) and, wide with
+narrow layers in between, [3,70,8,256,12,1]."""
 import math
 
 import numpy as np
@@ -23,7 +26,9 @@ pytestmark = pytest.mark.gpu
 DEVICE = "cuda"
 NS = [5, 16, 37]
 NETS = {"bench_narrow": [3, 64, 32, 1], "awkward": [3, 7, 1],
-        "bench_wide": [3, 256, 256, 1], "ragged_wide": [3, 70, 256, 1]}
+        "bench_wide": [3, 256, 256, 1], "ragged_wide": [3, 70, 256, 1],
+        "one_layer": [3, 1], "five_layers": [3, 16, 24, 8, 40, 1],
+        "five_layers_wide": [3, 70, 8, 256, 12, 1]}
 MODES = ["noised", "uniform"]
 STEPS = 6
 HORIZON = 4

@@ -7,7 +7,9 @@ initial weights — no tolerance.
 
 N = 5 (less than one tile), 16 (exactly one), 37 (two full tiles and a
 5-row tail).  Nets: the bench net [17,64,32,6] and [5,8,3], whose dims are
-no multiple of 4 or 16.  Cut patterns come from a small horizon: horizon 2
+no multiple of 4 or 16; the layer-count ends of the shared forward, [5,3]
+(one layer: the output stays in the first activation buffer) and the ragged
+[5,16,24,8,40,3] (five, MLP_MAX_LAYERS).  Cut patterns come from a small horizon: horizon 2
 with 3 steps cuts mid-epoch, horizon 3 with 3 steps cuts on the last step,
 horizon 2 with 4 steps cuts twice.  Carried across calls (is_continuous),
 horizon 2 with 3 steps alternates the patterns (1,) and (0, 2), so the
@@ -23,6 +25,8 @@ AWKWARD_ID = "RolloutFusedAwkward-v0"
 NETS = {
     "bench": ("HalfCheetah-v4", [17, 64, 32, 6]),
     "awkward": (AWKWARD_ID, [5, 8, 3]),
+    "one_layer": (AWKWARD_ID, [5, 3]),
+    "five_layers": (AWKWARD_ID, [5, 16, 24, 8, 40, 3]),
 }
 # name: (horizon, steps, cut patterns expected over three epochs when
 # every epoch resets, ... when state is carried)
@@ -139,3 +143,38 @@ def test_outside_gate_takes_three_kernel_body(monkeypatch):
         assert torch.isfinite(obs).all() and torch.isfinite(act).all()
         assert torch.isfinite(rew).all() and len(finals) == len(g.cuts)
         assert act.abs().sum() > 0 and obs[1:].abs().sum() > 0
+
+
+def test_binding_refuses_cuts_that_do_not_ascend():
+    """ppo_rollout_fused takes the cut list lockstep_cuts produces: strictly
+    ascending steps of the epoch.  Anything else is refused before the
+    launch, so slot j of cut_final belongs to cuts[j] alone."""
+    from rl_replicas_amd import ops
+    from rl_replicas_amd.networks import MLP
+    from rl_replicas_amd.ops.fused_mlp import _extract_layers
+
+    ext = ops._load_extension()
+    n, steps, O, A = 5, 6, 5, 3
+    torch.manual_seed(3)
+    weights, biases, acts = _extract_layers(MLP([O, 8, A]).to(DEVICE))
+    log_std = torch.zeros(A, device=DEVICE)
+    envA, envB = 0.1 * torch.randn(O, O, device=DEVICE), 0.1 * torch.randn(A, O, device=DEVICE)
+    envw = torch.randn(O, device=DEVICE)
+
+    def call(cuts):
+        obs_full = torch.full((steps + 1, n, O), -777.0, device=DEVICE)
+        ext.ppo_rollout_fused(
+            list(weights), list(biases), acts, log_std, envA, envB, envw, 0.0, 11, 12,
+            list(cuts), True, torch.full((1,), CTR_BASE, dtype=torch.int64, device=DEVICE),
+            obs_full, torch.zeros(steps, n, A, device=DEVICE),
+            torch.zeros(steps, n, device=DEVICE), torch.zeros(2, n, O, device=DEVICE))
+        torch.cuda.synchronize()
+        return obs_full
+
+    assert (call((1, 3)) != -777.0).all()
+    for cuts in ((3, 1), (2, 2)):  # unsorted, repeated
+        with pytest.raises(RuntimeError, match="ascending"):
+            call(cuts)
+    for cuts in ((6,), (-1,)):
+        with pytest.raises(RuntimeError, match="out of range"):
+            call(cuts)
