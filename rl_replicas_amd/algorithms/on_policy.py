@@ -99,7 +99,12 @@ class OnPolicyAlgorithm(AlgorithmBase):
 
     # ------------------------------------------------------------------
     def _prepare_batch(self, experience: Experience) -> Dict[str, Tensor]:
-        """Device-resident flat batch with advantages and returns.
+        """Device-resident flat batch with advantages and returns."""
+        return self._finish_batch(*self._upload_batch(experience), self.device)
+
+    def _upload_batch(self, experience: Experience):
+        """(flat, obs, actions, rewards, last_obs): the flat batch's fp32
+        payload on the device.
 
         On GPU the fp32 payload (obs | actions | rewards | last_obs) is
         packed into one cached pinned buffer and crosses in a single
@@ -113,7 +118,7 @@ class OnPolicyAlgorithm(AlgorithmBase):
             actions = flat["actions"].to(device=device, dtype=torch.float32)
             rewards = flat["rewards"].to(device)
             last_obs = flat["last_observations"].to(device)
-            return self._finish_batch(flat, obs, actions, rewards, last_obs, device)
+            return flat, obs, actions, rewards, last_obs
         obs_np = flat["observations"]
         act_np = np.asarray(flat["actions"], dtype=np.float32)
         rew_np = flat["rewards"]
@@ -147,7 +152,7 @@ class OnPolicyAlgorithm(AlgorithmBase):
             actions = torch.as_tensor(act_np, device=device)
             rewards = torch.as_tensor(rew_np, dtype=torch.float32, device=device)
             last_obs = torch.as_tensor(last_np, dtype=torch.float32, device=device)
-        return self._finish_batch(flat, obs, actions, rewards, last_obs, device)
+        return flat, obs, actions, rewards, last_obs
 
     def _finish_batch(self, flat, obs, actions, rewards, last_obs, device) -> Dict[str, Tensor]:
         offsets = torch.as_tensor(flat["episode_offsets"], device=device)
@@ -186,15 +191,20 @@ class OnPolicyAlgorithm(AlgorithmBase):
 
     # ------------------------------------------------------------------
     def train(self, experience: Experience) -> None:
-        batch = self._prepare_batch(experience)
-        obs = batch["observations"]
-        actions = batch["actions"]
-        advantages = batch["advantages"]
-        returns = batch["discounted_returns"]
+        uploaded = self._upload_batch(experience)
+        # an algorithm may take the whole train side of the epoch (batch
+        # preparation included) from the uploaded rollout
+        joint = self._train_epoch_fused(*uploaded)
+        if joint is None:
+            batch = self._finish_batch(*uploaded, self.device)
+            obs = batch["observations"]
+            actions = batch["actions"]
+            advantages = batch["advantages"]
+            returns = batch["discounted_returns"]
 
-        # the two updates are independent (advantages and returns come from
-        # the pre-update value net), so an algorithm may run them jointly
-        joint = self._update_policy_and_value(obs, actions, advantages, returns)
+            # the two updates are independent (advantages and returns come from
+            # the pre-update value net), so an algorithm may run them jointly
+            joint = self._update_policy_and_value(obs, actions, advantages, returns)
         if joint is not None:
             policy_metrics, value_loss = joint
         else:
@@ -215,6 +225,13 @@ class OnPolicyAlgorithm(AlgorithmBase):
     def _update_policy(self, obs: Tensor, actions: Tensor, advantages: Tensor) -> Dict[str, float]:
         """Algorithm-specific policy update; returns metric tag->value."""
         raise NotImplementedError
+
+    def _train_epoch_fused(self, flat, obs: Tensor, actions: Tensor, rewards: Tensor,
+                           last_obs: Tensor):
+        """Optional whole train side of an epoch from _upload_batch's result
+        (values, GAE, normalization and both updates): (policy metrics, mean
+        value loss), or None to prepare the batch and update as usual."""
+        return None
 
     def _update_policy_and_value(self, obs: Tensor, actions: Tensor, advantages: Tensor,
                                  returns: Tensor):

@@ -4,6 +4,14 @@ On the GPU the PPO/VPG policy update and the value-function loop bypass
 torch autograd entirely.  From fastest to most general, one PPO epoch's
 update runs as:
 
+  epoch graph (_GraphedPPOEpoch): the twin graph below with the batch
+      preparation in front and the old-policy sync behind — one eager
+      ppo_ingest_rows launch (three forwards over the rows, both log-probs,
+      the copies into the graph's buffers), then GAE, normalize, the
+      diagnostics, the pairs and ppo_epoch_epilogue in ONE graph, and one
+      readback.  Single-process fp32 Gaussian policies wherever the twin
+      graph is eligible (RL_REPLICAS_AMD_PPO_EPOCH_GRAPH=0 keeps the
+      separate batch preparation).
   twin graph (_GraphedPPOTwin): policy iteration i and value iteration i
       share two launches — a twin kernel that runs forward, loss seed and
       whole-net backward of both nets with LDS-resident activations, and a
@@ -725,26 +733,54 @@ class _GraphedPPOTwin:
 
     def __init__(self, algo, obs0: Tensor, actions0: Tensor, adv0: Tensor,
                  old_logp0: Tensor, returns0: Tensor):
-        from rl_replicas_amd.ops.fused_adam import adam_arg_lists
-
-        ext = ops._load_extension()
-        policy, vf = algo.policy, algo.value_function
-        pmlp, vmlp = _mlp_of(policy), vf.network
         dev = obs0.device
         self.obs = obs0.clone()
         self.actions = actions0.clone()
         self.adv = adv0.clone()
         self.old_logp = old_logp0.clone()
         self.returns = returns0.clone()
-        clip = float(algo.clip_range)
-        thr = 1.5 * float(algo.max_kl_divergence)
-        num_p = int(algo.num_policy_gradients)
-        num_v = int(algo.num_value_gradients)
-        assert 1 <= num_p <= num_v
         self.gate = torch.ones(1, device=dev)
         self.kl_final = torch.zeros(1, device=dev)
         self.loss0 = torch.zeros(1, device=dev)
         self.iters_done = torch.zeros(1, device=dev)
+        self._capture(algo)
+
+    # what a derived graph puts around the pairs -------------------------
+    def _head(self) -> None:
+        self.gate.fill_(1.0)
+        self.iters_done.zero_()
+
+    def _tail(self, algo, kl: Tensor) -> Tensor:
+        """Flush the pending KL, bump both optimizers' step counters and
+        finalize the value losses; returns the per-iteration losses."""
+        ext = ops._load_extension()
+        ext.ppo_gate_update_(self.gate, kl, self.kl_final, self.iters_done,
+                             self._thr)
+        # ... after which iters_done IS the executed-update count
+        algo.policy.optimizer.bump_steps_by(self.iters_done)
+        algo.value_function.optimizer.bump_steps(float(self._num_v))
+        return ext.value_loss_finalize(self.partials, self._fb)
+
+    def _extra_state(self, algo) -> List[Tensor]:
+        """Tensors beyond both nets and their Adam state that the warm-up
+        runs must leave as they found them."""
+        return []
+
+    def _capture(self, algo) -> None:
+        """Capture head, the P twin pairs, the V - P value pairs, the
+        flushed KL's forward and the tail over this object's buffers (obs,
+        actions, adv, old_logp, returns; gate, kl_final, loss0, iters_done)."""
+        from rl_replicas_amd.ops.fused_adam import adam_arg_lists
+
+        ext = ops._load_extension()
+        policy, vf = algo.policy, algo.value_function
+        pmlp, vmlp = _mlp_of(policy), vf.network
+        dev = self.obs.device
+        clip = float(algo.clip_range)
+        thr = self._thr = 1.5 * float(algo.max_kl_divergence)
+        num_p = int(algo.num_policy_gradients)
+        num_v = self._num_v = int(algo.num_value_gradients)
+        assert 1 <= num_p <= num_v
         scratch_loss = torch.zeros(1, device=dev)
 
         pw, pb, pacts = _extract_layers(pmlp)
@@ -761,13 +797,12 @@ class _GraphedPPOTwin:
         vm, vv, vstep, vhp = adam_arg_lists(vf.optimizer, vw, vb)
         state += [p.data for p in vf.parameters()]
         state += _ensure_adam_state(vf.optimizer)
-        fb = int(ext.value_loss_partials_blocks(obs0.shape[0]))
+        fb = self._fb = int(ext.value_loss_partials_blocks(self.obs.shape[0]))
         self.partials = torch.zeros(num_v, fb, device=dev)
         dummy = torch.empty(0, device=dev)
 
         def body():
-            self.gate.fill_(1.0)
-            self.iters_done.zero_()
+            self._head()
             for i in range(num_p):
                 twin_iter(
                     self.obs, list(pw), list(pb), pacts, self.actions,
@@ -785,20 +820,16 @@ class _GraphedPPOTwin:
                     float(i), True,
                 )
             # policy epilogue: the final executed iteration's KL is still
-            # pending; after it iters_done IS the executed-update count
+            # pending
             out = _forward_only(pmlp, self.obs)
             if kind == "gaussian":
                 kl = ext.gaussian_kl(out, self.actions, policy.log_std.data,
                                      self.old_logp)
             else:
                 kl = ext.categorical_kl(out, self.actions, self.old_logp)
-            ext.ppo_gate_update_(self.gate, kl, self.kl_final,
-                                 self.iters_done, thr)
-            policy.optimizer.bump_steps_by(self.iters_done)
-            vf.optimizer.bump_steps(float(num_v))
-            return ext.value_loss_finalize(self.partials, fb)
+            return self._tail(algo, kl)
 
-        self.loop = _CapturedLoop(body, state)
+        self.loop = _CapturedLoop(body, state + self._extra_state(algo))
 
     def run(self, algo, obs, actions, advantages, old_logp, returns):
         self.obs.copy_(obs)
@@ -817,6 +848,212 @@ class _GraphedPPOTwin:
             "policy/loss": float(self.loss0[0]),
             "policy/kl_divergence": float(self.kl_final[0]),
         }, float(losses.mean())
+
+
+class _GraphedPPOEpoch(_GraphedPPOTwin):
+    """The whole train side of a Gaussian-policy PPO epoch as one eager
+    launch, one graph replay and one readback.
+
+    ppo_ingest_rows (eager; the only launch that sees the epoch's tensor
+    addresses) runs the value net, the policy and the old policy once over
+    the T step rows + E bootstrap rows and fills this object's buffers.  The
+    graph then holds, in order: GAE and normalize writing `returns` / `adv`
+    where the pairs read them, the two pre-update diagnostics, the twin graph's
+    pairs and flushed KL, ppo_epoch_epilogue (gate bookkeeping, step bumps,
+    value-loss rows, old-policy sync, gate left open for the next replay) and
+    the mean value loss.  Everything the host reads lands in `metrics`:
+
+      [0] gate  [1] kl_final  [2] loss0  [3] iters_done (live, 0 between
+      replays)  [4] executed updates  [5] sum(log_std)  [6] std(logp)
+      [7] mean value loss
+
+    Every kernel runs the arithmetic of the launch it replaces on the same
+    values, so all results equal the twin path's bit for bit."""
+
+    GATE, KL, LOSS0, ITERS_LIVE, ITERS, LOG_STD_SUM, LOGP_STD, VALUE_LOSS = range(8)
+
+    def __init__(self, algo, obs: Tensor, actions: Tensor, rewards: Tensor,
+                 last_obs: Tensor, offsets: Tensor, dones: Tensor):
+        dev = obs.device
+        T, E = obs.shape[0], last_obs.shape[0]
+        self.obs = torch.empty_like(obs)
+        self.actions = torch.empty_like(actions)
+        self.rewards = torch.empty(T, device=dev)
+        self.offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        self.dones = torch.empty(E, dtype=torch.int32, device=dev)
+        self.values_all = torch.empty(T + E, device=dev)
+        self.old_logp = torch.empty(T, device=dev)
+        self.logp_now = torch.empty(T, device=dev)
+        self.adv_raw = torch.empty(T, device=dev)
+        self.adv = torch.empty(T, device=dev)
+        self.returns = torch.empty(T, device=dev)
+        self.losses = torch.empty(int(algo.num_value_gradients), device=dev)
+        self.metrics = torch.zeros(8, device=dev)
+        self.metrics[self.GATE] = 1.0
+        self.gate = self.metrics[self.GATE:self.GATE + 1]
+        self.kl_final = self.metrics[self.KL:self.KL + 1]
+        self.loss0 = self.metrics[self.LOSS0:self.LOSS0 + 1]
+        self.iters_done = self.metrics[self.ITERS_LIVE:self.ITERS_LIVE + 1]
+        # the warm-up runs of the capture need real rows in the buffers
+        self.ingest(algo, obs, actions, rewards, last_obs, offsets, dones)
+        self._capture(algo)
+
+    def ingest(self, algo, obs, actions, rewards, last_obs, offsets, dones) -> None:
+        ext = ops._load_extension()
+        policy, old = algo.policy, algo.old_policy
+        vw, vb, vacts = _extract_layers(algo.value_function.network)
+        pw, pb, pacts = _extract_layers(_mlp_of(policy))
+        ow, ob, _ = _extract_layers(_mlp_of(old))
+        ext.ppo_ingest_rows(
+            obs, last_obs, actions, rewards, offsets, dones,
+            list(vw), list(vb), vacts, list(pw), list(pb), pacts,
+            policy.log_std.data, list(ow), list(ob), old.log_std.data,
+            self.obs, self.actions, self.rewards, self.offsets, self.dones,
+            self.values_all, self.old_logp, self.logp_now,
+        )
+
+    def _head(self) -> None:
+        ext = ops._load_extension()
+        ext.segmented_gae_out(self.rewards, self.values_all, self.offsets,
+                              self.dones, self._gamma, self._lam, self.adv_raw,
+                              self.returns)
+        ext.normalize_out(self.adv_raw, self.adv)
+        # pre-update diagnostics; the entropy's constant is added on the host
+        torch.sum(self._log_std, dim=0, out=self.metrics[self.LOG_STD_SUM])
+        torch.std(self.logp_now, dim=0, out=self.metrics[self.LOGP_STD])
+
+    def _tail(self, algo, kl: Tensor) -> Tensor:
+        ext = ops._load_extension()
+        policy, vf = algo.policy, algo.value_function
+        src = policy.state_dict()
+        dst = algo.old_policy.state_dict()
+        assert list(src) == list(dst)
+        ext.ppo_epoch_epilogue_(
+            self.gate, kl, self.kl_final, self.iters_done,
+            self.metrics[self.ITERS:self.ITERS + 1], self._thr,
+            _step_counters(policy.optimizer), _step_counters(vf.optimizer),
+            float(self._num_v), self.partials, self._fb, self.losses,
+            list(src.values()), list(dst.values()),
+        )
+        torch.mean(self.losses, dim=0, out=self.metrics[self.VALUE_LOSS])
+        return self.losses
+
+    def _extra_state(self, algo) -> List[Tensor]:
+        # the graph no longer opens the gate at its head, and its tail
+        # overwrites the old policy
+        return [self.metrics] + [p.data for p in algo.old_policy.parameters()]
+
+    def _capture(self, algo) -> None:
+        self._gamma, self._lam = float(algo.gamma), float(algo.gae_lambda)
+        self._log_std = algo.policy.log_std.detach()
+        super()._capture(algo)
+
+    def run(self, algo, obs, actions, rewards, last_obs, offsets, dones):
+        self.ingest(algo, obs, actions, rewards, last_obs, offsets, dones)
+        self.loop.replay()
+        m = self.metrics.cpu()  # the epoch's one readback
+        iters = int(m[self.ITERS])
+        if iters < algo.num_policy_gradients:
+            logger.info(
+                "Early stopping at update %d due to reaching max KL divergence.",
+                iters - 1,
+            )
+        d = algo.policy.log_std.numel()
+        entropy = float(m[self.LOG_STD_SUM]) + 0.5 * d * (1.0 + math.log(2 * math.pi))
+        return {
+            "policy/loss": float(m[self.LOSS0]),
+            "policy/avarage_entropy": entropy,
+            "policy/log_prob_std": float(m[self.LOGP_STD]),
+            "policy/kl_divergence": float(m[self.KL]),
+        }, float(m[self.VALUE_LOSS])
+
+
+def _step_counters(optimizer) -> List[Tensor]:
+    """Every parameter's Adam step counter, in FusedAdam.bump_steps' order."""
+    return [
+        optimizer.state[p]["step"]
+        for group in optimizer.param_groups
+        for p in group["params"]
+        if p in optimizer.state and "step" in optimizer.state[p]
+    ]
+
+
+EPOCH_GRAPH_CACHE = 8  # graphs per algorithm, as DeviceSampler bounds its own
+
+
+def _epoch_graph_enabled() -> bool:
+    return os.environ.get("RL_REPLICAS_AMD_PPO_EPOCH_GRAPH", "1") != "0"
+
+
+def ppo_epoch_eligible(algo, obs: Tensor) -> bool:
+    """Whether ppo_epoch_update takes the epoch: the twin graph is eligible,
+    the policy is Gaussian in fp32, no data-parallel hook sits between GAE
+    and the update, and the ingest kernel holds the three nets in LDS.
+    RL_REPLICAS_AMD_PPO_EPOCH_GRAPH=0 keeps the twin path (batch prepared by
+    separate launches)."""
+    from rl_replicas_amd.algorithms.on_policy import OnPolicyAlgorithm
+
+    if not _epoch_graph_enabled() or ops.compute_bf16() != 0:
+        return False
+    if getattr(algo, "_dp_replicate", False) or getattr(algo, "_dp_enabled", False):
+        return False
+    for hook in ("_gather_global_batch", "_normalize_advantages"):
+        if getattr(type(algo), hook) is not getattr(OnPolicyAlgorithm, hook) \
+                or hook in vars(algo):
+            return False
+    if not (obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2):
+        return False
+    if _policy_kind(algo.policy) != "gaussian" or not ppo_twin_eligible(algo, obs):
+        return False
+    old_mlp = _mlp_of(getattr(algo, "old_policy", None) or algo.policy)
+    if old_mlp is None or _extract_layers(old_mlp) is None:
+        return False
+    ext = ops._load_extension()
+    max_width, budget = ext.ppo_ingest_rows_limits()
+    dims = []
+    for mlp in (algo.value_function.network, _mlp_of(algo.policy), old_mlp):
+        weights = _extract_layers(mlp)[0]
+        dims.append([int(weights[0].shape[1])] + [int(w.shape[0]) for w in weights])
+    vdims, pdims, odims = dims
+    if odims != pdims or max(vdims + pdims) > max_width:
+        return False
+    return int(ext.ppo_ingest_rows_lds_bytes(vdims, pdims)) <= budget
+
+
+def ppo_epoch_update(algo, flat, obs: Tensor, actions: Tensor, rewards: Tensor,
+                     last_obs: Tensor):
+    """The whole train side of one PPO epoch from the uploaded rollout
+    (_GraphedPPOEpoch): (policy metric dict, mean value loss), the values
+    _finish_batch + ppo_value_twin_update give; None when the epoch has to
+    take that path."""
+    if not ppo_epoch_eligible(algo, obs):
+        return None
+    policy = algo.policy
+    obs = obs.contiguous()
+    actions = actions.contiguous().view(obs.shape[0], -1)
+    if actions.shape[1] != policy.log_std.numel() or last_obs.shape[0] < 1:
+        return None
+    rewards = rewards.contiguous()
+    last_obs = last_obs.contiguous()
+    dev = obs.device
+    offsets = torch.as_tensor(flat["episode_offsets"], device=dev).to(torch.int32)
+    dones = torch.as_tensor(flat["episode_dones"], device=dev).to(torch.int32)
+    key = (tuple(obs.shape), tuple(actions.shape), int(last_obs.shape[0]),
+           int(algo.num_policy_gradients), int(algo.num_value_gradients),
+           float(algo.gamma), float(algo.gae_lambda),
+           tuple(id(p) for p in policy.parameters()),
+           tuple(id(p) for p in algo.value_function.parameters()),
+           tuple(id(p) for p in algo.old_policy.parameters()))
+    graphs = algo.__dict__.setdefault("_ppo_epoch_graphs", {})
+    graphed = graphs.get(key)
+    if graphed is None:
+        if len(graphs) >= EPOCH_GRAPH_CACHE:
+            return None
+        graphed = graphs[key] = _GraphedPPOEpoch(
+            algo, obs, actions, rewards, last_obs, offsets, dones
+        )
+    algo.epoch_graph_replays = getattr(algo, "epoch_graph_replays", 0) + 1
+    return graphed.run(algo, obs, actions, rewards, last_obs, offsets, dones)
 
 
 def _get_cached_graph(algo, attr: str, key, builder):

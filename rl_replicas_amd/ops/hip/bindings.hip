@@ -134,6 +134,8 @@ __global__ void synthetic_env_reset_kernel(float* s_out, int total,
 __global__ void counter_add_kernel(unsigned long long* ctr,
                                    unsigned long long delta);
 void launch_ppo_rollout_fused(const RolloutFusedArgs& a, hipStream_t stream);
+void launch_ppo_ingest_rows(const PPOIngestArgs& a, hipStream_t stream);
+__global__ void ppo_epoch_epilogue(PPOEpilogueArgs a);
 __global__ void segmented_gae_kernel(const float* rewards, const float* values,
                                      const float* last_values, const int* offsets,
                                      const int* dones, float* advantages,
@@ -873,6 +875,18 @@ std::vector<torch::Tensor> value_mlp_backward(torch::Tensor x,
 // ---------------------------------------------------------------------------
 // segmented GAE
 // ---------------------------------------------------------------------------
+// one workgroup of 256 per episode
+static void launch_segmented_gae(const float* rewards, const float* values,
+                                 const float* last_values, const int* offsets,
+                                 const int* dones, float* adv, float* ret, int n_eps,
+                                 double gamma, double lam) {
+  if (n_eps <= 0) return;
+  hipLaunchKernelGGL(segmented_gae_kernel, dim3(n_eps), dim3(256), 0,
+                     current_stream(), rewards, values, last_values, offsets, dones,
+                     adv, ret, (float)gamma, (float)lam);
+  HIP_OK(hipGetLastError());
+}
+
 std::vector<torch::Tensor> segmented_gae(torch::Tensor rewards, torch::Tensor values,
                                          torch::Tensor last_values,
                                          torch::Tensor offsets, torch::Tensor dones,
@@ -885,25 +899,58 @@ std::vector<torch::Tensor> segmented_gae(torch::Tensor rewards, torch::Tensor va
   const int n_eps = (int)last_values.size(0);
   auto adv = torch::empty_like(rewards);
   auto ret = torch::empty_like(rewards);
-  if (n_eps > 0) {
-    hipLaunchKernelGGL(segmented_gae_kernel, dim3(n_eps), dim3(256), 0,
-                       current_stream(), rewards.data_ptr<float>(),
-                       values.data_ptr<float>(), last_values.data_ptr<float>(),
-                       offsets.data_ptr<int>(), dones.data_ptr<int>(),
-                       adv.data_ptr<float>(), ret.data_ptr<float>(), (float)gamma,
-                       (float)lam);
-    HIP_OK(hipGetLastError());
-  }
+  launch_segmented_gae(rewards.data_ptr<float>(), values.data_ptr<float>(),
+                       last_values.data_ptr<float>(), offsets.data_ptr<int>(),
+                       dones.data_ptr<int>(), adv.data_ptr<float>(),
+                       ret.data_ptr<float>(), n_eps, gamma, lam);
   return {adv, ret};
+}
+
+// the same launch into the caller's buffers (the captured PPO epoch):
+// values_all = [values (T) | last_values (E)], as one forward leaves them
+void segmented_gae_out(torch::Tensor rewards, torch::Tensor values_all,
+                       torch::Tensor offsets, torch::Tensor dones, double gamma,
+                       double lam, torch::Tensor adv, torch::Tensor ret) {
+  check_f32_gpu(rewards, "rewards");
+  check_f32_gpu(values_all, "values_all");
+  check_f32_gpu(adv, "adv");
+  check_f32_gpu(ret, "ret");
+  const int64_t T = rewards.numel();
+  const int64_t n_eps = values_all.numel() - T;
+  TORCH_CHECK(n_eps >= 0 && adv.numel() == T && ret.numel() == T,
+              "segmented_gae_out: rewards/adv/ret [T], values_all [T + E]");
+  TORCH_CHECK(offsets.scalar_type() == torch::kInt32 && offsets.is_cuda() &&
+                  offsets.is_contiguous() && offsets.numel() == n_eps + 1,
+              "offsets must be a contiguous int32 GPU tensor [E + 1]");
+  TORCH_CHECK(dones.scalar_type() == torch::kInt32 && dones.is_cuda() &&
+                  dones.is_contiguous() && dones.numel() == n_eps,
+              "dones must be a contiguous int32 GPU tensor [E]");
+  launch_segmented_gae(rewards.data_ptr<float>(), values_all.data_ptr<float>(),
+                       values_all.data_ptr<float>() + T, offsets.data_ptr<int>(),
+                       dones.data_ptr<int>(), adv.data_ptr<float>(),
+                       ret.data_ptr<float>(), (int)n_eps, gamma, lam);
+}
+
+static void launch_normalize(const torch::Tensor& x, torch::Tensor& y) {
+  hipLaunchKernelGGL(normalize_kernel, dim3(1), dim3(1024), 0, current_stream(),
+                     x.data_ptr<float>(), y.data_ptr<float>(), (int)x.numel());
+  HIP_OK(hipGetLastError());
 }
 
 torch::Tensor normalize(torch::Tensor x) {
   check_f32_gpu(x, "x");
   auto y = torch::empty_like(x);
-  hipLaunchKernelGGL(normalize_kernel, dim3(1), dim3(1024), 0, current_stream(),
-                     x.data_ptr<float>(), y.data_ptr<float>(), (int)x.numel());
-  HIP_OK(hipGetLastError());
+  launch_normalize(x, y);
   return y;
+}
+
+// the same launch into the caller's buffer (x and y distinct)
+void normalize_out(torch::Tensor x, torch::Tensor y) {
+  check_f32_gpu(x, "x");
+  check_f32_gpu(y, "y");
+  TORCH_CHECK(y.numel() == x.numel() && y.data_ptr() != x.data_ptr(),
+              "normalize_out: y must be a second buffer of x's size");
+  launch_normalize(x, y);
 }
 
 torch::Tensor q_target(torch::Tensor r, torch::Tensor d, torch::Tensor qn,
@@ -1015,6 +1062,76 @@ torch::Tensor value_loss_finalize(torch::Tensor partials, int64_t fb) {
                      rows, (int)fb, stride);
   HIP_OK(hipGetLastError());
   return scalars;
+}
+
+// The captured PPO epoch's tail in one launch (ppo_epoch_epilogue,
+// update_kernels.hip): ppo_gate_update_ on the flushed KL, adam_bump_dev_ of
+// pol_steps by the executed-update count, adam_bump_ of val_steps by
+// val_bump, value_loss_finalize of partials into losses, and src -> dst for
+// every tensor of the old-policy sync.  iters_out receives the count the
+// host reads; gate = 1 and iters_done = 0 are left for the next replay.
+void ppo_epoch_epilogue_(torch::Tensor gate, torch::Tensor kl, torch::Tensor kl_final,
+                         torch::Tensor iters_done, torch::Tensor iters_out,
+                         double thr, std::vector<torch::Tensor> pol_steps,
+                         std::vector<torch::Tensor> val_steps, double val_bump,
+                         torch::Tensor partials, int64_t fb, torch::Tensor losses,
+                         std::vector<torch::Tensor> srcs,
+                         std::vector<torch::Tensor> dsts) {
+  PPOEpilogueArgs a{};
+  for (const torch::Tensor* t : {&gate, &kl, &kl_final, &iters_done, &iters_out}) {
+    check_f32_gpu(*t, "gate/kl/kl_final/iters_done/iters_out");
+    TORCH_CHECK(t->numel() >= 1, "gate bookkeeping scalars must not be empty");
+  }
+  TORCH_CHECK(gate.numel() == 1 && kl_final.numel() == 1 && iters_done.numel() == 1 &&
+                  iters_out.numel() == 1,
+              "gate bookkeeping scalars must have 1 element");
+  a.gate = gate.data_ptr<float>();
+  a.kl = kl.data_ptr<float>();
+  a.kl_final = kl_final.data_ptr<float>();
+  a.iters_done = iters_done.data_ptr<float>();
+  a.iters_out = iters_out.data_ptr<float>();
+  a.thr = (float)thr;
+  TORCH_CHECK(pol_steps.size() <= MT_MAX_TENSORS && val_steps.size() <= MT_MAX_TENSORS &&
+                  srcs.size() <= MT_MAX_TENSORS && srcs.size() == dsts.size(),
+              "ppo_epoch_epilogue_: at most ", MT_MAX_TENSORS,
+              " step counters per optimizer and synced tensors");
+  auto fill_steps = [](const std::vector<torch::Tensor>& steps, float** out) {
+    for (size_t i = 0; i < steps.size(); ++i) {
+      TORCH_CHECK(steps[i].is_cuda() && steps[i].scalar_type() == torch::kFloat32 &&
+                      steps[i].numel() == 1,
+                  "adam step must be a 1-element fp32 GPU tensor");
+      out[i] = steps[i].data_ptr<float>();
+    }
+  };
+  fill_steps(pol_steps, a.pol_step);
+  fill_steps(val_steps, a.val_step);
+  a.n_pol_steps = (int)pol_steps.size();
+  a.n_val_steps = (int)val_steps.size();
+  a.val_bump = (float)val_bump;
+  check_f32_gpu(partials, "partials");
+  check_f32_gpu(losses, "losses");
+  TORCH_CHECK(partials.dim() == 2, "partials must be [rows, stride]");
+  a.rows = (int)partials.size(0);
+  a.row_stride = (int)partials.size(1);
+  a.fb = (int)fb;
+  TORCH_CHECK(fb >= 0 && a.fb <= a.row_stride, "fb exceeds partials row stride");
+  TORCH_CHECK(losses.numel() == a.rows, "losses must hold one element per row");
+  a.partials = partials.data_ptr<float>();
+  a.losses = losses.data_ptr<float>();
+  a.n_sync = (int)srcs.size();
+  for (int i = 0; i < a.n_sync; ++i) {
+    check_f32_gpu(srcs[i], "sync source");
+    check_f32_gpu(dsts[i], "sync destination");
+    TORCH_CHECK(srcs[i].numel() == dsts[i].numel() &&
+                    srcs[i].numel() < (1LL << 31),
+                "sync source and destination differ in size");
+    a.src[i] = srcs[i].data_ptr<float>();
+    a.dst[i] = dsts[i].data_ptr<float>();
+    a.numel[i] = (int)srcs[i].numel();
+  }
+  hipLaunchKernelGGL(ppo_epoch_epilogue, dim3((a.rows + 3) / 4 + 1 + a.n_sync),
+                     dim3(256), 0, current_stream(), a);
+  HIP_OK(hipGetLastError());
 }
 
 void fused_polyak_(std::vector<torch::Tensor> srcs, std::vector<torch::Tensor> dsts,
@@ -2098,6 +2215,112 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
 }
 
 // ---------------------------------------------------------------------------
+// one pass over a PPO epoch's rows (ppo_ingest_kernels.hip)
+// ---------------------------------------------------------------------------
+static size_t ppo_ingest_lds_bytes(const NetLayout& v, const NetLayout& p) {
+  return (size_t)ppo_ingest_lds_floats(v.dims, v.L, p.dims, p.L) * sizeof(float);
+}
+
+// vdims / pdims = [obs, hidden..., 1] / [obs, hidden..., act_dim]
+int64_t ppo_ingest_rows_lds_bytes_py(std::vector<int64_t> vdims,
+                                     std::vector<int64_t> pdims) {
+  return (int64_t)ppo_ingest_lds_bytes(net_layout(vdims, ROLLOUT_MAX_WIDTH),
+                                       net_layout(pdims, ROLLOUT_MAX_WIDTH));
+}
+
+// Reads the epoch's tensors (observations [T, O], last_observations [E, O],
+// actions [T, A], rewards [T], offsets int32 [E + 1], dones int32 [E]) once
+// and writes the update graph's buffers: the copies obs_out / act_out /
+// rew_out / off_out / dones_out, values_all [T + E] from the value net,
+// logp_now [T] from the policy and old_logp [T] from the old policy (which
+// has the policy's shape and activations).
+void ppo_ingest_rows(torch::Tensor observations, torch::Tensor last_observations,
+                     torch::Tensor actions, torch::Tensor rewards,
+                     torch::Tensor offsets, torch::Tensor dones,
+                     std::vector<torch::Tensor> vweights,
+                     std::vector<torch::Tensor> vbiases, std::vector<int64_t> vacts,
+                     std::vector<torch::Tensor> pweights,
+                     std::vector<torch::Tensor> pbiases, std::vector<int64_t> pacts,
+                     torch::Tensor log_std, std::vector<torch::Tensor> oweights,
+                     std::vector<torch::Tensor> obiases, torch::Tensor old_log_std,
+                     torch::Tensor obs_out, torch::Tensor act_out,
+                     torch::Tensor rew_out, torch::Tensor off_out,
+                     torch::Tensor dones_out, torch::Tensor values_all,
+                     torch::Tensor old_logp, torch::Tensor logp_now) {
+  PPOIngestArgs a{};
+  const NetLayout pnet =
+      net_layout(observations, pweights, pbiases, pacts, ROLLOUT_MAX_WIDTH);
+  const NetLayout onet =
+      net_layout(observations, oweights, obiases, pacts, ROLLOUT_MAX_WIDTH);
+  const NetLayout vnet =
+      net_layout(observations, vweights, vbiases, vacts, ROLLOUT_MAX_WIDTH);
+  TORCH_CHECK(onet.L == pnet.L, "the old policy must have the policy's shape");
+  for (int l = 0; l <= pnet.L; ++l)
+    TORCH_CHECK(onet.dims[l] == pnet.dims[l], "the old policy must have the policy's shape");
+  TORCH_CHECK(vnet.dims[vnet.L] == 1, "ppo_ingest_rows: the value head must be 1 wide");
+  const torch::Device dev = observations.device();
+  check_net_device(pweights, pbiases, dev);
+  check_net_device(oweights, obiases, dev);
+  check_net_device(vweights, vbiases, dev);
+  TORCH_CHECK(ppo_ingest_lds_bytes(vnet, pnet) <= MLP_LDS_BUDGET,
+              "ppo_ingest_rows: net images exceed the LDS budget");
+
+  const int64_t T = observations.size(0), O = observations.size(1);
+  const int64_t A = pnet.dims[pnet.L];
+  check_f32_gpu(last_observations, "last_observations");
+  TORCH_CHECK(last_observations.dim() == 2 && last_observations.size(1) == O,
+              "last_observations must be [E, O]");
+  const int64_t E = last_observations.size(0);
+  TORCH_CHECK(T >= 1 && E >= 1 && T + E < (1LL << 24), "row count out of range");
+  for (const torch::Tensor* t : {&actions, &rewards, &log_std, &old_log_std})
+    check_f32_gpu(*t, "actions / rewards / log_std");
+  TORCH_CHECK(actions.numel() == T * A && rewards.numel() == T,
+              "actions must be [T, A] and rewards [T]");
+  TORCH_CHECK(log_std.numel() == A && old_log_std.numel() == A, "log_std must be [A]");
+  check_out(offsets, torch::kInt32, E + 1, "offsets");
+  check_out(dones, torch::kInt32, E, "dones");
+  check_out(obs_out, torch::kFloat32, T * O, "obs_out");
+  check_out(act_out, torch::kFloat32, T * A, "act_out");
+  check_out(rew_out, torch::kFloat32, T, "rew_out");
+  check_out(off_out, torch::kInt32, E + 1, "off_out");
+  check_out(dones_out, torch::kInt32, E, "dones_out");
+  check_out(values_all, torch::kFloat32, T + E, "values_all");
+  check_out(old_logp, torch::kFloat32, T, "old_logp");
+  check_out(logp_now, torch::kFloat32, T, "logp_now");
+  for (const torch::Tensor* t :
+       {&last_observations, &actions, &rewards, &offsets, &dones, &log_std,
+        &old_log_std, &obs_out, &act_out, &rew_out, &off_out, &dones_out,
+        &values_all, &old_logp, &logp_now})
+    TORCH_CHECK(t->device() == dev, "ppo_ingest_rows: tensors on different devices");
+
+  fill_net(a.val, vnet, vweights, vbiases, vacts);
+  fill_net(a.pol, pnet, pweights, pbiases, pacts);
+  fill_net(a.old, onet, oweights, obiases, pacts);
+  a.obs = observations.data_ptr<float>();
+  a.last_obs = last_observations.data_ptr<float>();
+  a.actions = actions.data_ptr<float>();
+  a.rewards = rewards.data_ptr<float>();
+  a.offsets = offsets.data_ptr<int>();
+  a.dones = dones.data_ptr<int>();
+  a.log_std = log_std.data_ptr<float>();
+  a.old_log_std = old_log_std.data_ptr<float>();
+  a.obs_out = obs_out.data_ptr<float>();
+  a.act_out = act_out.data_ptr<float>();
+  a.rew_out = rew_out.data_ptr<float>();
+  a.off_out = off_out.data_ptr<int>();
+  a.dones_out = dones_out.data_ptr<int>();
+  a.values_all = values_all.data_ptr<float>();
+  a.old_logp = old_logp.data_ptr<float>();
+  a.logp_now = logp_now.data_ptr<float>();
+  a.T = (int)T;
+  a.E = (int)E;
+  a.O = (int)O;
+  a.A = (int)A;
+  launch_ppo_ingest_rows(a, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
 // GPU-resident policy evaluation (eval_kernels.hip)
 // ---------------------------------------------------------------------------
 // the per-episode outputs of an evaluation: returns fp64 [N], lengths int32
@@ -2529,6 +2752,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether the reduce+Adam launch takes the LDS-staged kernel");
   m.def("segmented_gae", &segmented_gae, "segmented GAE+returns scan (gfx950)");
   m.def("normalize", &normalize, "fused mean/std normalize (gfx950)");
+  m.def("segmented_gae_out", &segmented_gae_out,
+        "segmented GAE+returns scan into the caller's buffers (gfx950)");
+  m.def("normalize_out", &normalize_out,
+        "fused mean/std normalize into the caller's buffer (gfx950)");
+  m.def("ppo_ingest_rows", &ppo_ingest_rows,
+        "one pass over a PPO epoch's rows: three forwards, two log-probs and "
+        "the copies into the update graph's buffers (gfx950)");
+  m.def("ppo_ingest_rows_lds_bytes", &ppo_ingest_rows_lds_bytes_py,
+        "dynamic LDS of ppo_ingest_rows for (value dims, policy dims)");
+  m.def("ppo_ingest_rows_limits",
+        []() {
+          return std::vector<int64_t>{ROLLOUT_MAX_WIDTH, (int64_t)MLP_LDS_BUDGET};
+        },
+        "(max width, LDS budget) of ppo_ingest_rows");
+  m.def("ppo_epoch_epilogue_", &ppo_epoch_epilogue_,
+        "the captured PPO epoch's tail in one launch (gfx950)");
   m.def("q_target", &q_target, "fused Q-learning target (gfx950)");
   m.def("td3_smooth", &td3_smooth,
         "TD3 target-policy smoothing: Philox noise + clip + limit (gfx950)",

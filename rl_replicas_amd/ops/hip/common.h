@@ -77,6 +77,25 @@ DEV_INLINE float wave_reduce_sum(float v) {
   return v;
 }
 
+// One row of the deferred value-loss finalize on one wave
+// (value_loss_finalize_rows, loss_kernels.hip, and ppo_epoch_epilogue,
+// update_kernels.hip): the wave loads 64 partials per coalesced access and
+// every lane then adds them lane by lane (v_readlane), in the serial order
+// from 0.f of loss_partials_finalize.  All 64 lanes must call it.
+DEV_INLINE void value_loss_row_sum(const float* __restrict__ partials,
+                                   float* __restrict__ scalars, int r, int fb,
+                                   int row_stride, int lane) {
+  const float* row = partials + (long)r * row_stride;
+  float s = 0.f;
+  for (int p0 = 0; p0 < fb; p0 += 64) {
+    const int v = p0 + lane < fb ? __float_as_int(row[p0 + lane]) : 0;
+    const int n = min(64, fb - p0);  // pads are never added
+    for (int p = 0; p < n; ++p)
+      s += __int_as_float(__builtin_amdgcn_readlane(v, p));
+  }
+  if (lane == 0) scalars[r] = s;
+}
+
 // Fused-MLP static limits.  Python reads them from the extension
 // (fused_mlp_limits); ops/fused_mlp.py keeps MAX_LAYERS / MAX_WIDTH for
 // hosts without it, and a GPU test holds the two equal.
@@ -395,6 +414,62 @@ struct CartPoleEvalArgs : NetArgs {  // dims[0] == 4 (obs), dims[L] == n_act
   const unsigned long long* reset_ctr;  // init-draw counter (read once)
   int N, horizon;
   uint64_t policy_seed, env_seed;
+};
+
+// one pass over a PPO epoch's rows (ppo_ingest_kernels.hip): a workgroup owns
+// ROLLOUT_ROWS of the T step rows + E bootstrap rows, runs the value net, the
+// current policy and the old policy on its LDS tile and copies the epoch's
+// tensors into the update graph's capture-stable buffers.  Narrow nets only.
+struct PPOIngestArgs {
+  NetArgs val, pol, old;     // old has the shape of pol
+  const float* obs;          // [T, O]
+  const float* last_obs;     // [E, O]
+  const float* actions;      // [T, A]
+  const float* rewards;      // [T]
+  const int* offsets;        // [E + 1]
+  const int* dones;          // [E]
+  const float* log_std;      // [A] of pol
+  const float* old_log_std;  // [A] of old
+  float* obs_out;            // [T, O]
+  float* act_out;            // [T, A]
+  float* rew_out;            // [T]
+  int* off_out;              // [E + 1]
+  int* dones_out;            // [E]
+  float* values_all;         // [T + E]
+  float* old_logp;           // [T]
+  float* logp_now;           // [T]
+  int T, E, O, A;
+};
+
+// its LDS floats: the row tile + 2 activation tiles, three net images and
+// the two sigma tables
+__host__ __device__ inline long ppo_ingest_lds_floats(const int* vdims, int vl,
+                                                      const int* pdims, int pl) {
+  return net_lds_floats(3, vdims, vl) + 2 * net_lds_floats(0, pdims, pl) +
+         2 * pdims[pl];
+}
+
+// the tail of the captured PPO epoch (ppo_epoch_epilogue, update_kernels.hip):
+// the flushed KL's gate bookkeeping, both optimizers' step bumps, the deferred
+// value-loss rows and the old-policy sync, then the gate left open again
+struct PPOEpilogueArgs {
+  float* gate;               // left at 1 for the next replay
+  const float* kl;           // the last executed iteration's pending KL
+  float* kl_final;
+  float* iters_done;         // left at 0 for the next replay
+  float* iters_out;          // the executed-update count, for the host
+  float thr;
+  float* pol_step[MT_MAX_TENSORS];  // += executed-update count
+  float* val_step[MT_MAX_TENSORS];  // += val_bump
+  int n_pol_steps, n_val_steps;
+  float val_bump;
+  const float* partials;     // [rows][row_stride], fb used per row
+  float* losses;             // [rows]
+  int rows, fb, row_stride;
+  const float* src[MT_MAX_TENSORS];  // policy parameters ...
+  float* dst[MT_MAX_TENSORS];        // ... copied to the old policy's
+  int numel[MT_MAX_TENSORS];
+  int n_sync;
 };
 
 // the multi-kernel body's ring write (offpolicy_kernels.hip): the buffers

@@ -17,6 +17,7 @@
 // reductions: bitwise deterministic, and at B<=32K rows the whole loss
 // is latency-bound anyway.
 #include "common.h"
+#include "rollout_steps.h"
 
 #define LOSS_THREADS 1024
 
@@ -218,18 +219,9 @@ __global__ void loss_partials_finalize(const float* __restrict__ partials,
 __global__ __launch_bounds__(256) void value_loss_finalize_rows(
     const float* __restrict__ partials, float* __restrict__ scalars, int rows,
     int fb, int row_stride) {
-  const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;  // wave-uniform
-  const float* row = partials + (long)r * row_stride;
-  float s = 0.f;
-  for (int p0 = 0; p0 < fb; p0 += 64) {
-    const int v = p0 + lane < fb ? __float_as_int(row[p0 + lane]) : 0;
-    const int n = min(64, fb - p0);  // pads are never added
-    for (int p = 0; p < n; ++p)
-      s += __int_as_float(__builtin_amdgcn_readlane(v, p));
-  }
-  if (lane == 0) scalars[r] = s;
+  value_loss_row_sum(partials, scalars, r, fb, row_stride, threadIdx.x & 63);
 }
 
 // logp only (old-policy snapshot at epoch start)
@@ -241,20 +233,11 @@ __global__ __launch_bounds__(LOSS_THREADS) void gaussian_logp_kernel(
   __shared__ float s_base;
   for (int d = threadIdx.x; d < D; d += LOSS_THREADS)
     s_sigma[d] = __expf(log_std[d]);
-  if (threadIdx.x == 0) {
-    float b = 0.f;
-    for (int d = 0; d < D; ++d) b += log_std[d];
-    s_base = b + 0.5f * (float)D * LOG_2PI;
-  }
+  if (threadIdx.x == 0) s_base = gaussian_logp_base(log_std, D);
   __syncthreads();
-  for (int r = tid; r < B; r += gridDim.x * LOSS_THREADS) {
-    float q = 0.f;
-    for (int d = 0; d < D; ++d) {
-      const float z = (actions[(long)r * D + d] - mean[(long)r * D + d]) / s_sigma[d];
-      q += z * z;
-    }
-    logp[r] = -0.5f * q - s_base;
-  }
+  for (int r = tid; r < B; r += gridDim.x * LOSS_THREADS)
+    logp[r] = gaussian_logp_row(actions, (long)r * D, mean, (long)r * D, s_sigma,
+                                s_base, D);
 }
 
 // approx KL = mean(old_logp - logp(mean_new))  (ppo.py:259-269)

@@ -4,7 +4,7 @@
 // env step and reset kernels, replay_scatter_kernel) and the persistent
 // kernels (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip,
 // pendulum_rollout_kernels.hip, pendulum_collect_kernels.hip,
-// eval_kernels.hip).  Every caller inlines the SAME expressions in the SAME
+// eval_kernels.hip, ppo_ingest_kernels.hip).  Every caller inlines the SAME expressions in the SAME
 // order, so both routes produce the same bytes; the operands may live in
 // global memory or in LDS.
 //
@@ -186,6 +186,28 @@ DEV_INLINE int cut_slot(const int* cut_step, int n_cuts, int t) {
   for (int c = 0; c < n_cuts; ++c)
     if (cut_step[c] == t) slot = c;
   return slot;
+}
+
+// Diagonal-Gaussian log-prob of one row (gaussian_logp_kernel, loss_kernels.hip,
+// and ppo_ingest_rows_f32, ppo_ingest_kernels.hip): the caller tabulates
+// sigma[d] = __expf(log_std[d]) and the row-independent base once, then every
+// row sums its squared z in d order.
+DEV_INLINE float gaussian_logp_base(const float* log_std, int D) {
+  float b = 0.f;
+  for (int d = 0; d < D; ++d) b += log_std[d];
+  return b + 0.5f * (float)D * LOG_2PI;
+}
+
+// The row's actions start at actions[aoff], its means at mean[moff].
+DEV_INLINE float gaussian_logp_row(const float* __restrict__ actions, long aoff,
+                                   const float* __restrict__ mean, long moff,
+                                   const float* sigma, float base, int D) {
+  float q = 0.f;
+  for (int d = 0; d < D; ++d) {
+    const float z = (actions[aoff + d] - mean[moff + d]) / sigma[d];
+    q += z * z;
+  }
+  return -0.5f * q - base;
 }
 
 // one uniform action element in [low, high], keyed by (seed, offset, i)

@@ -80,6 +80,55 @@ __global__ void ppo_gate_update_kernel(float* gate, const float* kl,
   }
 }
 
+// The tail of the captured PPO epoch in one launch, replacing
+// ppo_gate_update_kernel, adam_step_bump_dev_kernel, adam_step_bump_kernel,
+// value_loss_finalize_rows and the per-tensor old-policy copies.  Workgroups
+// [0, ceil(rows / 4)) finalize the value-loss rows (one wave per row), the
+// next one does the bookkeeping, and one workgroup per parameter tensor
+// copies the policy into the old policy: a plain load and store, so every
+// bit pattern (-0.0f, NaN payloads) arrives as it is.  The bookkeeping is
+// the three small kernels' arithmetic in their order on one thread, the step
+// bumps on thread t of the same workgroup; it then hands the host its copy
+// of the executed-update count and leaves gate = 1, iters_done = 0 behind,
+// which is what the next replay's first iteration expects.
+__global__ __launch_bounds__(256) void ppo_epoch_epilogue(PPOEpilogueArgs a) {
+  const int row_blocks = (a.rows + 3) / 4;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (b < row_blocks) {
+    const int r = b * 4 + (tid >> 6);
+    if (r >= a.rows) return;  // wave-uniform
+    value_loss_row_sum(a.partials, a.losses, r, a.fb, a.row_stride, tid & 63);
+    return;
+  }
+  if (b == row_blocks) {
+    __shared__ float s_done;
+    if (tid == 0) {
+      if (*a.gate != 0.f) {
+        *a.kl_final = *a.kl;
+        *a.iters_done += 1.f;
+        if (*a.kl > a.thr) *a.gate = 0.f;
+      }
+      s_done = *a.iters_done;
+    }
+    __syncthreads();
+    const float done = s_done;
+    if (tid < a.n_pol_steps) a.pol_step[tid][0] += done;
+    if (tid < a.n_val_steps) a.val_step[tid][0] += a.val_bump;
+    if (tid == 0) {
+      *a.iters_out = done;
+      *a.iters_done = 0.f;
+      *a.gate = 1.f;
+    }
+    return;
+  }
+  const int t = b - row_blocks - 1;
+  if (t >= a.n_sync) return;
+  const float* s = a.src[t];
+  float* d = a.dst[t];
+  for (int i = tid; i < a.numel[t]; i += 256) d[i] = s[i];
+}
+
 __global__ __launch_bounds__(256) void fused_polyak_kernel(PolyakArgs a) {
   const int t = blockIdx.x;
   if (t >= a.n_tensors) return;

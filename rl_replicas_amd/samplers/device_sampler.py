@@ -84,6 +84,7 @@ class DeviceSampler(Sampler):
         self._bufs = None  # eager-path buffers, reused across epochs
         self._graphs: Dict[tuple, object] = {}
         self._graph_ctr: Optional[torch.Tensor] = None
+        self._episode_indices: Dict[tuple, tuple] = {}
 
     def _get_bufs(self, steps: int, obs_dim: int, act_dim: int, device):
         if self._bufs is None or self._bufs[0].shape[0] != steps:
@@ -192,6 +193,28 @@ class DeviceSampler(Sampler):
         return obs_buf, act_buf, rew_buf, finals
 
     # ------------------------------------------------------------------
+    def _episode_index(self, steps: int, cuts: Tuple[int, ...]):
+        """(episode_offsets [N*n_segs + 1], episode_dones [N*n_segs]) of an
+        epoch as int32 device tensors.  Both are host arithmetic of (steps,
+        cuts, N), so each pattern is uploaded once and then shared, read-only,
+        by every experience that has it."""
+        key = (steps, cuts)
+        cached = self._episode_indices.get(key)
+        if cached is None:
+            N = self.num_envs
+            seg_bounds = segment_bounds(steps, cuts)
+            offsets_np = np.zeros(N * len(seg_bounds) + 1, dtype=np.int32)
+            np.cumsum(np.tile([e - s for s, e, _ in seg_bounds], N), out=offsets_np[1:])
+            dones_np = np.tile(np.asarray([d for _, _, d in seg_bounds], dtype=np.int32), N)
+            device = self.env.device
+            if len(self._episode_indices) >= 64:  # patterns cycle; keep it bounded
+                self._episode_indices.clear()
+            cached = self._episode_indices[key] = (
+                torch.as_tensor(offsets_np, device=device),
+                torch.as_tensor(dones_np, device=device),
+            )
+        return cached
+
     def _build_experience(self, steps: int, cuts: Tuple[int, ...], obs_buf,
                           act_buf, rew_buf, finals, obs_dim: int,
                           act_dim: int) -> Experience:
@@ -215,9 +238,8 @@ class DeviceSampler(Sampler):
         last_obs = torch.stack(lasts, dim=1).reshape(N * n_segs, obs_dim)
 
         seg_lengths = [e - s for s, e, _ in seg_bounds]
-        offsets_np = np.zeros(N * n_segs + 1, dtype=np.int32)
-        np.cumsum(np.tile(seg_lengths, N), out=offsets_np[1:])
         dones_pattern = [d for _, _, d in seg_bounds]
+        episode_offsets, episode_dones = self._episode_index(steps, cuts)
 
         # one tiny D2H: per-episode returns for the metrics layer
         seg_returns = torch.stack(
@@ -248,10 +270,8 @@ class DeviceSampler(Sampler):
                 "observations": flat_obs,
                 "actions": flat_act,
                 "rewards": flat_rew,
-                "episode_offsets": torch.as_tensor(offsets_np, device=device),
-                "episode_dones": torch.as_tensor(
-                    np.tile(dones_pattern, N), device=device
-                ),
+                "episode_offsets": episode_offsets,
+                "episode_dones": episode_dones,
                 "last_observations": last_obs,
                 "next_observations": flat_next,
                 "step_dones": step_dones.reshape(-1),

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "env_kernels.hip"),
         os.path.join(HIP_DIR, "rollout_kernels.hip"),
         os.path.join(HIP_DIR, "rollout_fused_kernels.hip"),
+        os.path.join(HIP_DIR, "ppo_ingest_kernels.hip"),
         os.path.join(HIP_DIR, "cartpole_rollout_kernels.hip"),
         os.path.join(HIP_DIR, "pendulum_rollout_kernels.hip"),
         os.path.join(HIP_DIR, "pendulum_collect_kernels.hip"),
