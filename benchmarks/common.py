@@ -91,18 +91,26 @@ def build_on_policy(env_id: str, seed: int, device: Optional[str], num_envs: int
 
 def build_off_policy(env_id: str, seed: int, device: Optional[str], num_envs: int,
                      twin: bool, env_mode: str = "cpu", eval_mode: str = "host"):
-    """eval_mode "device": a DeviceEvaluator, which runs Pendulum-v1 /
+    """env_mode "device": a DeviceReplaySampler over the env's device
+    implementation (Pendulum-v1 or a synthetic MuJoCo-shaped env), whose
+    collect phase writes straight into the buffer's ring on a GPU and is
+    DeviceSampler's eager loop elsewhere.
+
+    eval_mode "device": a DeviceEvaluator, which runs Pendulum-v1 /
     CartPole-v1 evaluation episodes on the policy's device and every other
     env as the host Evaluator does."""
     assert eval_mode in ("host", "device"), eval_mode
     set_seed_for_libraries(seed)
     dev = pick_device(device)
     buffer = ReplayBuffer(int(1e6), device=dev if dev.startswith("cuda") else None)
-    if env_mode == "device" and env_id == "Pendulum-v1":
+    if env_mode == "device":
         # the collect phase writes straight into the buffer's ring
         from rl_replicas_amd.samplers import DeviceReplaySampler
 
-        env = envs.DevicePendulumEnv(num_envs=num_envs, device=dev)
+        if env_id == "Pendulum-v1":
+            env = envs.DevicePendulumEnv(num_envs=num_envs, device=dev)
+        else:
+            env = envs.DeviceVectorEnv(env_id, num_envs=num_envs, device=dev)
         sampler = DeviceReplaySampler(env, buffer, seed=seed)
     else:
         env, sampler = make_sampler(env_id, seed, num_envs, is_continuous=True,

@@ -1,6 +1,6 @@
 """hipGraph-captured device rollouts, replay collection and evaluation.
 
-One construction, six classes.  The eager device loops issue 3 kernels per
+One construction, seven classes.  The eager device loops issue 3 kernels per
 env step (fused MLP forward, Philox action sample, fused env transition);
 here a whole epoch (reset or state carry, steps x [forward -> sample -> env
 step], the trailing nodes, one RNG-counter bump) is captured once and
@@ -37,6 +37,10 @@ What differs per class:
                           DevicePendulumEnv (DeviceReplaySampler), written
                           straight into a ReplayBuffer's HBM ring;
                           `pendulum_collect_fused`.
+  GraphedSyntheticCollect the same two behaviour policies on the synthetic
+                          DeviceVectorEnv (DeviceReplaySampler), any O and A
+                          up to one wave; the graph owns the carry [N, O];
+                          `synthetic_collect_fused`.
   GraphedPendulumEval /   whole evaluation episodes (DeviceEvaluator), only
   GraphedCartPoleEval     per-episode return, length and init state come
                           back; `pendulum_eval_fused` / `cartpole_eval_fused`.
@@ -641,6 +645,233 @@ class GraphedPendulumCollect:
         touched = (buffer._write + torch.arange(min(2 * n, cap), device=dev)) % cap
         kept = [t[touched] for t in storage]
         self.loop = fop._CapturedLoop(body, [self.ctr, state, write_dev, size_dev])
+        for t, k in zip(storage, kept):
+            t[touched] = k
+
+    def replay(self) -> None:
+        self.loop.replay()
+        self.buffer.advance_host(self.env.num_envs * self.steps)
+
+
+# ---------------------------------------------------------------------------
+# Off-policy replay collection on the synthetic envs (DeviceReplaySampler)
+# ---------------------------------------------------------------------------
+def _scalar_bounds(space):
+    """(low, high) of a Box every dimension of which has the same finite
+    bounds, else None: the sample kernels take scalar bounds."""
+    import numpy as np
+
+    if not (hasattr(space, "low") and hasattr(space, "high")):
+        return None
+    lo, hi = np.asarray(space.low).reshape(-1), np.asarray(space.high).reshape(-1)
+    if (lo.size < 1 or lo.size != hi.size or not np.isfinite([lo[0], hi[0]]).all()
+            or lo[0] > hi[0] or (lo != lo[0]).any() or (hi != hi[0]).any()):
+        return None
+    return float(lo[0]), float(hi[0])
+
+
+def synthetic_collect_mode(policy, env):
+    """Which behaviour policy of OffPolicyAlgorithm.learn `policy` is on a
+    synthetic DeviceVectorEnv with observations O and actions A wide:
+    COLLECT_NOISED (a utils._NoisedPolicy over a DeterministicPolicy over an
+    fp32 MLP [O, ..., A] the fused-MLP kernels take, on the env's device),
+    COLLECT_UNIFORM (a RandomPolicy over a Box with one finite low and one
+    finite high shared by every dimension, equal to the env's), or None."""
+    from rl_replicas_amd.policies import DeterministicPolicy, RandomPolicy
+    from rl_replicas_amd.utils import _NoisedPolicy
+
+    O, A = int(env.A.shape[0]), int(env.B.shape[0])
+    if isinstance(policy, RandomPolicy):
+        bounds = _scalar_bounds(policy.action_space)
+        if (bounds is None or bounds != _scalar_bounds(env.action_space)
+                or tuple(policy.action_space.shape) != (A,)):
+            return None
+        return COLLECT_UNIFORM
+    if isinstance(policy, _NoisedPolicy) and isinstance(policy.base_policy,
+                                                        DeterministicPolicy):
+        mlp = fop._mlp_of(policy.base_policy)
+        layers = _extract_layers(mlp) if mlp is not None else None
+        if layers is None or policy.action_noise_scale < 0 or policy.action_limit < 0:
+            return None
+        weights, biases, _ = layers
+        if (int(weights[0].shape[1]) != O or int(weights[-1].shape[0]) != A
+                or any(t.dtype != torch.float32 or t.device != env.A.device
+                       for t in (*weights, *biases))):
+            return None
+        return COLLECT_NOISED
+    return None
+
+
+def synthetic_collect_supported(policy, env, buffer) -> bool:
+    """A behaviour policy of `learn()` on a GPU DeviceVectorEnv whose
+    ReplayBuffer lives on the same device, with the extension present and
+    graphs enabled."""
+    from rl_replicas_amd.envs.device import DeviceVectorEnv
+
+    if not _env_ready(env, DeviceVectorEnv):
+        return False
+    if buffer is None or buffer.device is None or buffer.device.type != "cuda":
+        return False
+    if torch.empty(0, device=buffer.device).device != env.A.device:
+        return False
+    return synthetic_collect_mode(policy, env) is not None
+
+
+def synthetic_collect_fused_default() -> bool:
+    """Which body a synthetic-env collect graph takes when
+    RL_REPLICAS_AMD_ROLLOUT_FUSED is unset.  The persistent kernel is the
+    default only where it beat the multi-kernel body by more than the larger
+    of the two bodies' run-to-run spread at both off-policy shapes (1 x 50,
+    10 x 5) and in both modes (profiles/bench_synthetic_collect_1gpu.json,
+    docs/ARCHITECTURE.md)."""
+    return False
+
+
+def synthetic_collect_fused_eligible(policy, env, cuts: Tuple[int, ...]) -> bool:
+    """synthetic_collect_fused (synthetic_collect_kernels.hip) takes the
+    collect epoch: O and A at most one wave wide, an actor [O, ..., A] or no
+    net at all (the uniform draw), net + env image within the LDS budget and
+    a cut list within the binding's own limits."""
+    mode = synthetic_collect_mode(policy, env)
+    if mode is None:
+        return False
+    ext = ops._load_extension()
+    O, A = int(env.A.shape[0]), int(env.B.shape[0])
+    limits = ext.synthetic_collect_fused_limits()
+    # one wave carries a row: ROLLOUT_MAX_WIDTH, as ppo_rollout_fused has it
+    if max(O, A) > ext.ppo_rollout_fused_limits()[1]:
+        return False
+    if mode == COLLECT_UNIFORM and ext.synthetic_collect_fused_lds_bytes([], O, A) > limits[-1]:
+        return False
+    # COLLECT_NOISED already means fp32 weights and biases [O, ..., A], so the
+    # gate's own dtype and width checks cannot change the answer here
+    weights = _weights_of(policy.base_policy) if mode == COLLECT_NOISED else None
+    return _fused_gate(weights, (), limits,
+                       lambda dims: ext.synthetic_collect_fused_lds_bytes(dims, O, A),
+                       O, A, cuts, default=synthetic_collect_fused_default())
+
+
+class GraphedSyntheticCollect:
+    """One captured off-policy collect epoch on a synthetic DeviceVectorEnv,
+    written straight into a ReplayBuffer's HBM ring at the write position the
+    buffer holds on the device.
+
+    Fused body (`synthetic_collect_fused_eligible`): synthetic_collect_fused,
+    ring_advance_, counter_add_.  Multi-kernel body: synthetic_env_reset or
+    the carry copy, steps x ([mlp_forward -> gaussian_sample with noise scale
+    / limit] or uniform_sample, then synthetic_env_step), then
+    replay_scatter, ring_advance_, counter_add_.  Both write the same bytes.
+
+    `DeviceVectorEnv` replaces `env.state` on every eager step, so the graph
+    owns the carry: `carry` [N, O] holds the live state before a replay (the
+    sampler copies it in) and after it.  Keyed (steps, cuts,
+    start_with_reset, mode) by the sampler.  Philox offsets (both bodies,
+    `GraphedRollout`'s layout): action of step t at `t + ctr` (action seed),
+    dynamics noise at `2t + ctr`, autoreset at `2t + 1 + ctr`, epoch reset at
+    `2 * steps + ctr` (env seed); the counter advances by 2 * steps + 1.
+    Warm-up leaves no trace: the counter, the carry and both ring scalars are
+    restored by `_CapturedLoop`, the ring rows the warm-up runs wrote are put
+    back here."""
+
+    def __init__(self, policy, env, buffer, steps: int, cuts: Tuple[int, ...],
+                 start_with_reset: bool, mode: str, ctr: torch.Tensor):
+        ext = ops._load_extension()
+        N, O, A = env.num_envs, int(env.A.shape[0]), int(env.B.shape[0])
+        dev = env.device
+        n = N * steps
+        cap = buffer.buffer_size
+        assert n <= cap
+        self.env = env
+        self.buffer = buffer
+        self.steps = steps
+        self.cuts = list(cuts)
+        self.start_with_reset = start_with_reset
+        self.mode = mode
+        self.ctr = ctr
+        self.n_segs = len(cuts) + (1 if not cuts or cuts[-1] != steps - 1 else 0)
+        # the one read-back of an epoch
+        self.seg_returns = torch.zeros(N, self.n_segs, device=dev)
+        storage, write_dev, size_dev = buffer.device_ring(O, (A,))
+        env_seed = env._philox_seed
+        base_seed = torch.initial_seed()
+        compute_bf16 = ops.compute_bf16()
+        low, high = _scalar_bounds(env.action_space) or (0.0, 0.0)
+        if mode == COLLECT_NOISED:
+            weights, biases, acts = _extract_layers(fop._mlp_of(policy.base_policy))
+            weights, biases = list(weights), list(biases)
+            action_seed = (base_seed ^ _NOISE_SALT) & 0x7FFFFFFFFFFFFFFF
+            noise_scale = float(policy.action_noise_scale)
+            limit = float(policy.action_limit)
+            dummy_log_std = torch.zeros(A, device=dev)
+        else:
+            weights, biases, acts = [], [], []
+            action_seed = (base_seed ^ _UNIFORM_SALT) & 0x7FFFFFFFFFFFFFFF
+            noise_scale, limit = 0.0, 0.0
+
+        self.fused = synthetic_collect_fused_eligible(policy, env, cuts)
+        wide_threads = collect_wide_threads()
+
+        if self.fused:
+            self.carry = torch.zeros(N, O, device=dev)
+
+            def body():
+                ext.synthetic_collect_fused(
+                    weights, biases, acts, _COLLECT_MODE_CODE[mode], noise_scale,
+                    limit, low, high, action_seed, env_seed, env.A, env.B, env.w,
+                    env.noise, list(cuts), start_with_reset, self.ctr, self.carry,
+                    steps, storage, write_dev, size_dev, self.seg_returns,
+                    wide_threads,
+                )
+                ext.ring_advance_(write_dev, size_dev, n, cap)
+                ext.counter_add_(self.ctr, 2 * steps + 1)
+        else:
+            self.obs_full = torch.zeros(steps + 1, N, O, device=dev)
+            self.act_buf = torch.zeros(steps, N, A, device=dev)
+            self.rew_buf = torch.zeros(steps, N, device=dev)
+            self.cut_final = torch.zeros(max(len(cuts), 1), N, O, device=dev)
+            self.carry = self.obs_full[steps]
+            cset = {c: j for j, c in enumerate(cuts)}
+            cut_slot = torch.tensor([cset.get(t, -1) for t in range(steps)],
+                                    dtype=torch.int32, device=dev)
+
+            def body():
+                if start_with_reset:
+                    ext.synthetic_env_reset(N, O, env.A, env_seed, 2 * steps,
+                                            self.ctr, self.obs_full[0])
+                else:
+                    self.obs_full[0].copy_(self.obs_full[steps])
+                for t in range(steps):
+                    if mode == COLLECT_NOISED:
+                        mean = ext.mlp_forward(self.obs_full[t], weights, biases,
+                                               acts, False, compute_bf16)[0]
+                        ext.gaussian_sample(mean, dummy_log_std, action_seed, t,
+                                            noise_scale, limit, self.ctr,
+                                            self.act_buf[t])
+                    else:
+                        ext.uniform_sample(self.act_buf[t], low, high, action_seed,
+                                           t, self.ctr)
+                    do_reset = t in cset
+                    ext.synthetic_env_step(
+                        self.obs_full[t], self.act_buf[t], env.A, env.B, env.w,
+                        env.noise, env_seed, 2 * t, do_reset, self.ctr,
+                        self.obs_full[t + 1],
+                        self.cut_final[cset[t]] if do_reset else self.obs_full[t + 1],
+                        self.rew_buf[t],
+                    )
+                ext.replay_scatter(self.obs_full, self.act_buf, self.rew_buf,
+                                   self.cut_final, cut_slot, len(cuts), storage,
+                                   write_dev, size_dev, self.seg_returns)
+                ext.ring_advance_(write_dev, size_dev, n, cap)
+                # past every offset used: env 2t / 2t+1 (t<steps), reset
+                # 2*steps, action t (t<steps)
+                ext.counter_add_(self.ctr, 2 * steps + 1)
+
+        # the two warm-up runs write ring rows [write, write + 2n): keep what
+        # they held, so warm-up never costs a stored transition
+        touched = (buffer._write + torch.arange(min(2 * n, cap), device=dev)) % cap
+        kept = [t[touched] for t in storage]
+        self.loop = fop._CapturedLoop(
+            body, [self.ctr, self.carry, write_dev, size_dev])
         for t, k in zip(storage, kept):
             t[touched] = k
 

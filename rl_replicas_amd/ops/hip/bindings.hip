@@ -106,6 +106,8 @@ __global__ void pendulum_env_reset_kernel(double* state, float* obs, int N,
                                           int draw, uint64_t seed, uint64_t offset,
                                           const unsigned long long* offset_ptr);
 void launch_pendulum_rollout_fused(const PendulumRolloutArgs& a, hipStream_t stream);
+void launch_synthetic_collect_fused(const SyntheticCollectArgs& a, int wide_threads,
+                                    hipStream_t stream);
 void launch_pendulum_collect_fused(const PendulumCollectArgs& a, int wide_threads,
                                    hipStream_t stream);
 void launch_pendulum_eval_fused(const PendulumEvalArgs& a, int wide_threads,
@@ -2096,16 +2098,17 @@ void pendulum_rollout_fused(std::vector<torch::Tensor> weights,
 }
 
 // ---------------------------------------------------------------------------
-// Pendulum replay collection: device-side ring writes
+// Replay collection: device-side ring writes
 // ---------------------------------------------------------------------------
-// The replay ring handed to a collect kernel: storage = [observations [cap,3],
-// actions [cap,1], rewards [cap], next_observations [cap,3], dones [cap]],
+// The replay ring handed to a collect kernel: storage = [observations [cap,O],
+// actions [cap,A], rewards [cap], next_observations [cap,O], dones [cap]],
 // all contiguous fp32 on `dev`, both scalars 1-element int64 there, and room
-// for the epoch's n transitions without a slot written twice.
+// for the epoch's n transitions without a slot written twice.  O and A are
+// the storage tensors' own floats per slot, which must be the caller's.
 static ReplayRing check_ring(const std::vector<torch::Tensor>& storage,
                              const torch::Tensor& write_dev,
                              const torch::Tensor& size_dev, int64_t n,
-                             const torch::Device& dev) {
+                             const torch::Device& dev, int64_t O, int64_t A) {
   TORCH_CHECK(storage.size() == 5,
               "ring storage must be [obs, act, rew, next_obs, dones]");
   static const char* names[5] = {"ring observations", "ring actions", "ring rewards",
@@ -2117,7 +2120,11 @@ static ReplayRing check_ring(const std::vector<torch::Tensor>& storage,
   }
   const int64_t cap = storage[2].numel();
   TORCH_CHECK(cap >= 1, "empty ring");
-  const int64_t per_slot[5] = {3, 1, 1, 3, 1};
+  const int64_t ring_O = storage[0].numel() / cap, ring_A = storage[1].numel() / cap;
+  TORCH_CHECK(ring_O == O && ring_A == A, "the ring holds ", ring_O,
+              "-wide observations and ", ring_A, "-wide actions, the epoch's are ", O,
+              " and ", A, " wide");
+  const int64_t per_slot[5] = {O, A, 1, O, 1};
   for (int i = 0; i < 5; ++i)
     TORCH_CHECK(storage[i].size(0) == cap && storage[i].numel() == cap * per_slot[i],
                 names[i], " must hold ", per_slot[i], " floats per ring slot");
@@ -2135,6 +2142,8 @@ static ReplayRing check_ring(const std::vector<torch::Tensor>& storage,
   r.dn = storage[4].data_ptr<float>();
   r.write = reinterpret_cast<const long long*>(write_dev.data_ptr<int64_t>());
   r.cap = (unsigned long long)cap;
+  r.O = (int)O;
+  r.A = (int)A;
   return r;
 }
 
@@ -2171,7 +2180,7 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
   a.N = check_pendulum_carry(state);
   a.steps = check_step_count(steps, "steps");
   a.ring = check_ring(storage, write_dev, size_dev, (int64_t)a.N * steps,
-                      state.device());
+                      state.device(), 3, 1);
   TORCH_CHECK(mode == COLLECT_NOISED || mode == COLLECT_UNIFORM, "unknown mode");
   a.mode = (int)mode;
   NetLayout net;  // no layers in uniform mode
@@ -2211,6 +2220,104 @@ void pendulum_collect_fused(std::vector<torch::Tensor> weights,
   a.action_seed = (uint64_t)action_seed;
   a.env_seed = (uint64_t)env_seed;
   launch_pendulum_collect_fused(a, (int)wide_threads, current_stream());
+  HIP_OK(hipGetLastError());
+}
+
+static size_t synthetic_collect_lds_bytes(const NetLayout& n, int O, int A) {
+  return (size_t)synthetic_collect_lds_floats(n.dims, n.L, O, A) * sizeof(float);
+}
+
+// dims = [O, hidden..., A] of the actor; empty for the uniform draw
+int64_t synthetic_collect_fused_lds_bytes_py(std::vector<int64_t> dims, int64_t O,
+                                             int64_t A) {
+  TORCH_CHECK(O >= 1 && O <= ROLLOUT_MAX_WIDTH && A >= 1 && A <= ROLLOUT_MAX_WIDTH,
+              "synthetic_collect_fused: obs/action dims must be in [1, ",
+              ROLLOUT_MAX_WIDTH, "]");
+  NetLayout n;
+  if (!dims.empty()) n = net_layout(dims, MLP_MAX_WIDTH);
+  return (int64_t)synthetic_collect_lds_bytes(n, (int)O, (int)A);
+}
+
+// whole-epoch replay collection on a synthetic env in one launch
+// (synthetic_collect_kernels.hip): writes the epoch's N * steps transitions
+// into the ring at the device-held write position, seg_returns and the carry
+// [N, O]; reads the RNG counter and the ring scalars, never advances them
+// (ring_advance_ and counter_add_ follow).  mode COLLECT_UNIFORM takes no
+// net.  wide_threads: workgroup size of the wide regime, 256 or 1024.
+void synthetic_collect_fused(std::vector<torch::Tensor> weights,
+                             std::vector<torch::Tensor> biases,
+                             std::vector<int64_t> acts, int64_t mode,
+                             double noise_scale, double limit, double low,
+                             double high, int64_t action_seed, int64_t env_seed,
+                             torch::Tensor envA, torch::Tensor envB,
+                             torch::Tensor envw, double sigma,
+                             std::vector<int64_t> cuts, bool start_with_reset,
+                             torch::Tensor ctr, torch::Tensor carry, int64_t steps,
+                             std::vector<torch::Tensor> storage,
+                             torch::Tensor write_dev, torch::Tensor size_dev,
+                             torch::Tensor seg_returns, int64_t wide_threads) {
+  check_f32_gpu(carry, "carry");
+  check_f32_gpu(envA, "env A");
+  check_f32_gpu(envB, "env B");
+  check_f32_gpu(envw, "env w");
+  TORCH_CHECK(carry.dim() == 2 && carry.size(0) >= 1, "carry must be [N, O]");
+  TORCH_CHECK(envB.dim() == 2, "env B must be [A, O]");
+  SyntheticCollectArgs a{};
+  a.N = (int)carry.size(0);
+  a.O = (int)carry.size(1);
+  a.A = (int)envB.size(0);
+  TORCH_CHECK(a.O >= 1 && a.O <= ROLLOUT_MAX_WIDTH && a.A >= 1 &&
+                  a.A <= ROLLOUT_MAX_WIDTH,
+              "synthetic_collect_fused: obs/action dims must be in [1, ",
+              ROLLOUT_MAX_WIDTH, "]");
+  TORCH_CHECK(envA.dim() == 2 && envA.size(0) == a.O && envA.size(1) == a.O &&
+                  envB.size(1) == a.O && envw.dim() == 1 && envw.numel() == a.O,
+              "env matrices must be A[O,O], B[A,O], w[O]");
+  for (const torch::Tensor* t : {&envA, &envB, &envw})
+    TORCH_CHECK(t->device() == carry.device(), "the env matrices are on another device");
+  a.steps = check_step_count(steps, "steps");
+  a.ring = check_ring(storage, write_dev, size_dev, (int64_t)a.N * steps,
+                      carry.device(), a.O, a.A);
+  TORCH_CHECK(mode == COLLECT_NOISED || mode == COLLECT_UNIFORM, "unknown mode");
+  a.mode = (int)mode;
+  NetLayout net;  // no layers in uniform mode
+  if (mode == COLLECT_NOISED) {
+    net = net_layout(a.O, weights, biases, acts, MLP_MAX_WIDTH);
+    TORCH_CHECK(net.dims[net.L] == a.A,
+                "synthetic_collect_fused: the actor head width must equal the action dim");
+    check_net_device(weights, biases, carry.device());
+    TORCH_CHECK(noise_scale >= 0.0 && limit >= 0.0,
+                "synthetic_collect_fused: noise_scale and limit must be >= 0");
+    fill_net(a, net, weights, biases, acts);
+  } else {
+    TORCH_CHECK(weights.empty() && biases.empty() && acts.empty(),
+                "synthetic_collect_fused: uniform mode takes no net");
+    TORCH_CHECK(low <= high, "synthetic_collect_fused: low > high");
+  }
+  TORCH_CHECK(synthetic_collect_lds_bytes(net, a.O, a.A) <= MLP_LDS_BUDGET,
+              "synthetic_collect_fused: net + env image exceeds the LDS budget");
+  TORCH_CHECK(wide_threads == 256 || wide_threads == 1024,
+              "synthetic_collect_fused: wide_threads must be 256 or 1024");
+  fill_cuts(a, cuts, steps, "synthetic_collect_fused");
+  a.n_segs = epoch_segments(cuts, steps);
+  check_out(seg_returns, torch::kFloat32, (int64_t)a.N * a.n_segs, "seg_returns");
+  TORCH_CHECK(seg_returns.device() == carry.device(),
+              "seg_returns is on another device");
+  a.ctr = ctr_ptr(c10::optional<torch::Tensor>(ctr));
+  a.envA = envA.data_ptr<float>();
+  a.envB = envB.data_ptr<float>();
+  a.envw = envw.data_ptr<float>();
+  a.carry = carry.data_ptr<float>();
+  a.seg_returns = seg_returns.data_ptr<float>();
+  a.start_with_reset = start_with_reset ? 1 : 0;
+  a.noise_scale = (float)noise_scale;
+  a.limit = (float)limit;
+  a.low = (float)low;
+  a.high = (float)high;
+  a.sigma = (float)sigma;
+  a.action_seed = (uint64_t)action_seed;
+  a.env_seed = (uint64_t)env_seed;
+  launch_synthetic_collect_fused(a, (int)wide_threads, current_stream());
   HIP_OK(hipGetLastError());
 }
 
@@ -2488,7 +2595,8 @@ void uniform_sample(torch::Tensor out, double low, double high, int64_t seed,
 }
 
 // the multi-kernel body's ring write: the epoch buffers of steps x (action
-// -> pendulum_env_step) into the slots pendulum_collect_fused writes.
+// -> env step) into the slots the persistent collect kernels write.  O and A
+// come from obs_full and act_buf and must be the ring's.
 // cut_slot [steps] int32: index into cut_final on cut steps, -1 elsewhere.
 void replay_scatter(torch::Tensor obs_full, torch::Tensor act_buf,
                     torch::Tensor rew_buf, torch::Tensor cut_final,
@@ -2497,22 +2605,24 @@ void replay_scatter(torch::Tensor obs_full, torch::Tensor act_buf,
                     torch::Tensor size_dev, torch::Tensor seg_returns) {
   check_f32_gpu(obs_full, "obs_full");
   TORCH_CHECK(obs_full.dim() == 3 && obs_full.size(0) >= 2 && obs_full.size(1) >= 1 &&
-                  obs_full.size(2) == 3,
-              "obs_full must be [steps+1, N, 3]");
+                  obs_full.size(2) >= 1,
+              "obs_full must be [steps+1, N, O]");
+  TORCH_CHECK(act_buf.dim() == 3 && act_buf.size(2) >= 1, "act_buf must be [steps, N, A]");
   ReplayScatterArgs a{};
   a.steps = (int)obs_full.size(0) - 1;
   a.N = (int)obs_full.size(1);
+  const int64_t O = obs_full.size(2), A = act_buf.size(2);
   const int64_t SN = (int64_t)a.steps * a.N;
-  a.ring = check_ring(storage, write_dev, size_dev, SN, obs_full.device());
-  check_out(act_buf, torch::kFloat32, SN, "act_buf");
+  a.ring = check_ring(storage, write_dev, size_dev, SN, obs_full.device(), O, A);
+  check_out(act_buf, torch::kFloat32, SN * A, "act_buf");
   check_out(rew_buf, torch::kFloat32, SN, "rew_buf");
   check_out(cut_slot, torch::kInt32, a.steps, "cut_slot");
   TORCH_CHECK(n_cuts >= 0 && n_cuts <= a.steps, "n_cuts out of range");
   a.n_cuts = (int)n_cuts;
   check_f32_gpu(cut_final, "cut_final");
   TORCH_CHECK(cut_final.dim() == 3 && cut_final.size(0) >= std::max(a.n_cuts, 1) &&
-                  cut_final.size(1) == a.N && cut_final.size(2) == 3,
-              "cut_final must be [n_cuts, N, 3]");
+                  cut_final.size(1) == a.N && cut_final.size(2) == O,
+              "cut_final must be [n_cuts, N, O]");
   check_f32_gpu(seg_returns, "seg_returns");
   TORCH_CHECK(seg_returns.dim() == 2 && seg_returns.size(0) == a.N &&
                   seg_returns.size(1) >= std::max(a.n_cuts, 1),
@@ -2526,7 +2636,9 @@ void replay_scatter(torch::Tensor obs_full, torch::Tensor act_buf,
   a.cut_final = cut_final.data_ptr<float>();
   a.cut_slot = cut_slot.data_ptr<int>();
   a.seg_returns = seg_returns.data_ptr<float>();
-  hipLaunchKernelGGL(replay_scatter_kernel, dim3(std::min(256, (a.N + 255) / 256)),
+  const int64_t elems = SN * (2 * O + A);
+  hipLaunchKernelGGL(replay_scatter_kernel,
+                     dim3((unsigned)std::min<int64_t>(256, (elems + 255) / 256)),
                      dim3(256), 0, current_stream(), a);
   HIP_OK(hipGetLastError());
 }
@@ -2596,12 +2708,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         "(max layers, max width, max cuts, LDS budget in bytes) of "
         "pendulum_collect_fused");
+  m.def("synthetic_collect_fused", &synthetic_collect_fused,
+        "whole-epoch synthetic-env replay collection in one persistent kernel (gfx950)",
+        py::arg("weights"), py::arg("biases"), py::arg("acts"), py::arg("mode"),
+        py::arg("noise_scale"), py::arg("limit"), py::arg("low"), py::arg("high"),
+        py::arg("action_seed"), py::arg("env_seed"), py::arg("envA"),
+        py::arg("envB"), py::arg("envw"), py::arg("sigma"), py::arg("cuts"),
+        py::arg("start_with_reset"), py::arg("ctr"), py::arg("carry"),
+        py::arg("steps"), py::arg("storage"), py::arg("write_dev"),
+        py::arg("size_dev"), py::arg("seg_returns"), py::arg("wide_threads"));
+  m.def("synthetic_collect_fused_lds_bytes", &synthetic_collect_fused_lds_bytes_py,
+        "dynamic LDS of synthetic_collect_fused for an actor [O, ..., A] "
+        "(empty dims: the uniform draw)");
+  m.def("synthetic_collect_fused_limits",
+        []() {
+          return std::vector<int64_t>{MLP_MAX_LAYERS, MLP_MAX_WIDTH,
+                                      ROLLOUT_MAX_CUTS, (int64_t)MLP_LDS_BUDGET};
+        },
+        "(max layers, max width, max cuts, LDS budget in bytes) of "
+        "synthetic_collect_fused");
   m.def("uniform_sample", &uniform_sample,
         "Philox uniform actions in [low, high] (gfx950)", py::arg("out"),
         py::arg("low"), py::arg("high"), py::arg("seed"), py::arg("offset"),
         py::arg("offset_ctr") = py::none());
   m.def("replay_scatter", &replay_scatter,
-        "ring write of one captured Pendulum epoch's buffers (gfx950)",
+        "ring write of one captured collect epoch's buffers (gfx950)",
         py::arg("obs_full"), py::arg("act_buf"), py::arg("rew_buf"),
         py::arg("cut_final"), py::arg("cut_slot"), py::arg("n_cuts"),
         py::arg("storage"), py::arg("write_dev"), py::arg("size_dev"),

@@ -358,13 +358,14 @@ struct PendulumRolloutArgs : NetArgs {  // dims[0] == 3 (obs), dims[L] == 1 (tor
 // Kernels reduce *write modulo cap before use, so no value of the scalar
 // can index outside the storage.
 struct ReplayRing {
-  float* obs;   // [cap, 3]
-  float* act;   // [cap, 1]
+  float* obs;   // [cap, O]
+  float* act;   // [cap, A]
   float* rew;   // [cap]
-  float* nxt;   // [cap, 3]
+  float* nxt;   // [cap, O]
   float* dn;    // [cap]
   const long long* write;  // device scalar: next slot to write
   unsigned long long cap;
+  int O, A;     // floats per slot of obs / nxt and of act (Pendulum: 3, 1)
 };
 
 // persistent Pendulum replay collection (pendulum_collect_kernels.hip): one
@@ -388,6 +389,39 @@ struct PendulumCollectArgs : NetArgs {
   float low, high;           // uniform mode
   uint64_t action_seed, env_seed;
 };
+
+// persistent replay collection on the synthetic envs
+// (synthetic_collect_kernels.hip): one workgroup carries ROLLOUT_ROWS rows
+// through all `steps` iterations of behaviour action -> synthetic transition
+// / lockstep autoreset -> ring write.  dims[0] == O, dims[L] == A;
+// n_layers == 0 in uniform mode.  O == ring.O, A == ring.A.
+struct SyntheticCollectArgs : NetArgs {
+  const float* envA;       // [O, O]
+  const float* envB;       // [A, O]
+  const float* envw;       // [O]
+  float* carry;            // [N, O] live state (read unless start_with_reset)
+  ReplayRing ring;
+  float* seg_returns;      // [N, n_segs] per-row segment reward sums
+  const unsigned long long* ctr;  // device RNG counter (read once)
+  int cut_step[ROLLOUT_MAX_CUTS];  // ascending
+  int n_cuts, n_segs;
+  int N, O, A, steps;
+  int start_with_reset;
+  int mode;                // COLLECT_NOISED | COLLECT_UNIFORM
+  float noise_scale, limit;  // noised mode
+  float low, high;           // uniform mode
+  float sigma;               // env dynamics noise
+  uint64_t action_seed, env_seed;
+};
+
+// its LDS floats: 2 state tiles (step ping-pong) + 2 activation tiles + 1
+// action tile and the net, then env A/B/w.  The launcher, the binding's
+// budget check and the Python gate all size from here.
+__host__ __device__ inline long synthetic_collect_lds_floats(const int* dims,
+                                                             int n_layers, int O,
+                                                             int A) {
+  return net_lds_floats(5, dims, n_layers) + O * O + A * O + O;
+}
 
 // persistent policy evaluation (eval_kernels.hip): one workgroup carries
 // ROLLOUT_ROWS episodes from their init draw to their end and writes only
@@ -473,12 +507,12 @@ struct PPOEpilogueArgs {
 };
 
 // the multi-kernel body's ring write (offpolicy_kernels.hip): the buffers
-// of steps x (action -> pendulum_env_step) into the same slots
+// of steps x (action -> env step) into the same slots; O = ring.O, A = ring.A
 struct ReplayScatterArgs {
-  const float* obs_full;   // [steps + 1, N, 3]
-  const float* act_buf;    // [steps, N, 1]
+  const float* obs_full;   // [steps + 1, N, O]
+  const float* act_buf;    // [steps, N, A]
   const float* rew_buf;    // [steps, N]
-  const float* cut_final;  // [n_cuts, N, 3]
+  const float* cut_final;  // [n_cuts, N, O]
   const int* cut_slot;     // [steps]: index into cut_final, -1 off the cuts
   ReplayRing ring;
   float* seg_returns;      // [N, n_segs]

@@ -94,34 +94,47 @@ __global__ __launch_bounds__(256) void replay_gather_kernel(
   }
 }
 
-// Ring write of one captured Pendulum epoch (the multi-kernel body of
-// ops/fused_rollout.py::GraphedPendulumCollect): one thread per instance
-// walks its `steps` transitions in order and writes them to the slots
-// (write + row * steps + t) % cap — the slots, values and segment sums of
-// pendulum_collect_fused_f32.  Cut steps store the pre-reset successor from
-// cut_final and done = 1.
+// Ring write of one captured collect epoch (the multi-kernel bodies of
+// ops/fused_rollout.py::GraphedPendulumCollect / GraphedSyntheticCollect):
+// the epoch's buffers go to the slots (write + row * steps + t) % cap, the
+// slots, values and segment sums of the persistent collect kernels, for any
+// O = ring.O and A = ring.A.  Cut steps store the pre-reset successor from
+// cut_final and done = 1.  Two passes over disjoint outputs: the O + O + A
+// row elements of every transition, one thread each; then one thread per
+// instance walks its rewards in step order (the segment sums' order).
 __global__ __launch_bounds__(256) void replay_scatter_kernel(ReplayScatterArgs a) {
   const unsigned long long cap = a.ring.cap;
   const unsigned long long write = (unsigned long long)*a.ring.write % cap;
-  const int N = a.N, steps = a.steps;
+  const int N = a.N, steps = a.steps, O = a.ring.O, A = a.ring.A;
+  const int row_elems = 2 * O + A;
+  const long total = (long)N * steps * row_elems;
+  for (long i = blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int e = (int)(i % row_elems);
+    const long rt = i / row_elems;
+    const int t = (int)(rt % steps), row = (int)(rt / steps);
+    const unsigned long long slot = ring_slot(write, cap, row, steps, t);
+    if (e < O) {
+      a.ring.obs[slot * O + e] = a.obs_full[((long)t * N + row) * O + e];
+    } else if (e < 2 * O) {
+      const int k = e - O;
+      int cslot = a.cut_slot[t];
+      if (cslot >= a.n_cuts) cslot = -1;  // device data: never past cut_final
+      a.ring.nxt[slot * O + k] = cslot >= 0
+                                     ? a.cut_final[((long)cslot * N + row) * O + k]
+                                     : a.obs_full[((long)(t + 1) * N + row) * O + k];
+    } else {
+      const int d = e - 2 * O;
+      a.ring.act[slot * A + d] = a.act_buf[((long)t * N + row) * A + d];
+    }
+  }
   for (int row = blockIdx.x * 256 + threadIdx.x; row < N; row += gridDim.x * 256) {
     float seg_acc = 0.f;
     int cslot = -1;
     for (int t = 0; t < steps; ++t) {
       cslot = a.cut_slot[t];
-      if (cslot >= a.n_cuts) cslot = -1;  // device data: never past cut_final
-      const float* const ob = a.obs_full + ((long)t * N + row) * 3;
-      const float* const nx = cslot >= 0
-                                  ? a.cut_final + ((long)cslot * N + row) * 3
-                                  : a.obs_full + ((long)(t + 1) * N + row) * 3;
+      if (cslot >= a.n_cuts) cslot = -1;
       const unsigned long long slot = ring_slot(write, cap, row, steps, t);
-      #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        a.ring.obs[slot * 3 + k] = ob[k];
-        a.ring.nxt[slot * 3 + k] = nx[k];
-      }
       const float rew = a.rew_buf[(long)t * N + row];
-      a.ring.act[slot] = a.act_buf[(long)t * N + row];
       a.ring.rew[slot] = rew;
       a.ring.dn[slot] = cslot >= 0 ? 1.f : 0.f;
       seg_acc += rew;

@@ -4,7 +4,7 @@
 // env step and reset kernels, replay_scatter_kernel) and the persistent
 // kernels (rollout_fused_kernels.hip, cartpole_rollout_kernels.hip,
 // pendulum_rollout_kernels.hip, pendulum_collect_kernels.hip,
-// eval_kernels.hip, ppo_ingest_kernels.hip).  Every caller inlines the SAME expressions in the SAME
+// synthetic_collect_kernels.hip, eval_kernels.hip, ppo_ingest_kernels.hip).  Every caller inlines the SAME expressions in the SAME
 // order, so both routes produce the same bytes; the operands may live in
 // global memory or in LDS.
 //

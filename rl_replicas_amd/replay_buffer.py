@@ -172,7 +172,8 @@ class ReplayBuffer:
         pos = self._write
         first = min(n, self.buffer_size - pos)
         for key, t in batch.items():
-            t = t.to(dev, non_blocking=True)
+            # a copy down to a host ring is read at once below: it must block
+            t = t.to(dev, non_blocking=dev.type == "cuda")
             self._storage[key][pos : pos + first] = t[:first]
             if first < n:
                 self._storage[key][: n - first] = t[first:]

@@ -1,12 +1,19 @@
 """Device-resident replay collection — the off-policy twin of DeviceSampler.
 
-Pairs `envs.DevicePendulumEnv` with one `ReplayBuffer` on the same GPU.  An
-epoch of DDPG/TD3 collection (warm-up `RandomPolicy` or the noised actor) is
-ONE captured hipGraph (`ops/fused_rollout.py::GraphedPendulumCollect`) that
-steps the env and writes every transition straight into the buffer's HBM
-ring at the write position the buffer holds on the device.  Nothing is
+Pairs `envs.DevicePendulumEnv` or a synthetic `envs.DeviceVectorEnv` with one
+`ReplayBuffer` on the same GPU.  An epoch of DDPG/TD3 collection (warm-up
+`RandomPolicy` or the noised actor) is ONE captured hipGraph
+(`ops/fused_rollout.py::GraphedPendulumCollect` / `GraphedSyntheticCollect`)
+that steps the env and writes every transition straight into the buffer's
+HBM ring at the write position the buffer holds on the device.  Nothing is
 staged, transposed or copied a second time; the only read-back of an epoch
 is the per-episode returns for the metrics layer.
+
+The Pendulum env carries its fp64 `state` in place.  `DeviceVectorEnv`
+replaces `env.state` with a fresh tensor on every eager step, so there the
+graph owns a stable carry buffer: `sample()` copies the live state into it
+before the replay when that is another tensor, and points `env.state` at it
+afterwards.
 
 The returned `Experience` carries the episode structure (`episode_returns`,
 `episode_lengths`, `dones`, as `DeviceSampler._build_experience` orders
@@ -25,11 +32,11 @@ host, batch_sampler.py:55-99).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
-from rl_replicas_amd.envs.device import DevicePendulumEnv
+from rl_replicas_amd.envs.device import DevicePendulumEnv, DeviceVectorEnv
 from rl_replicas_amd.experience import Experience
 from rl_replicas_amd.policies import Policy
 from rl_replicas_amd.replay_buffer import ReplayBuffer
@@ -42,8 +49,8 @@ from rl_replicas_amd.samplers.device_sampler import (
 
 
 class DeviceReplaySampler(DeviceSampler):
-    def __init__(self, device_env: DevicePendulumEnv, replay_buffer: ReplayBuffer,
-                 seed: Optional[int] = None):
+    def __init__(self, device_env: Union[DevicePendulumEnv, DeviceVectorEnv],
+                 replay_buffer: ReplayBuffer, seed: Optional[int] = None):
         super().__init__(device_env, seed=seed, is_continuous=True)
         buffer_device = replay_buffer.device
         if device_env.device.type == "cuda" and (
@@ -61,15 +68,26 @@ class DeviceReplaySampler(DeviceSampler):
         env = self.env
         N = self.num_envs
         buffer = self.replay_buffer
+        synthetic = isinstance(env, DeviceVectorEnv)
+        if synthetic:
+            supported, mode_of, graph_cls = (
+                fused_rollout.synthetic_collect_supported,
+                fused_rollout.synthetic_collect_mode,
+                fused_rollout.GraphedSyntheticCollect)
+        else:
+            supported, mode_of, graph_cls = (
+                fused_rollout.pendulum_collect_supported,
+                fused_rollout.pendulum_collect_mode,
+                fused_rollout.GraphedPendulumCollect)
         if (num_samples % N != 0 or num_samples > buffer.buffer_size
-                or not fused_rollout.pendulum_collect_supported(policy, env, buffer)):
+                or not supported(policy, env, buffer)):
             return super().sample(num_samples, policy)
         steps = num_samples // N
         first = self._obs is None
         horizon = env.spec.max_episode_steps
         start_elapsed = 0 if first else env._elapsed
         cuts = lockstep_cuts(steps, horizon, start_elapsed)
-        mode = fused_rollout.pendulum_collect_mode(policy, env)
+        mode = mode_of(policy, env)
         key = (steps, cuts, first, mode)
         g = self._graphs.get(key)
         if g is None:
@@ -79,11 +97,19 @@ class DeviceReplaySampler(DeviceSampler):
                 env.seed(self.seed)
             g = cached_graph(
                 self, key,
-                lambda ctr: fused_rollout.GraphedPendulumCollect(
+                lambda ctr: graph_cls(
                     policy, env, buffer, steps, cuts, first, mode, ctr),
             )
-        g.replay()
-        self._obs = g.last_obs
+        if synthetic:
+            # the live state into the graph's carry (nothing to do when the
+            # previous epoch was this graph's)
+            if not first and self._obs is not g.carry:
+                g.carry.copy_(self._obs)
+            g.replay()
+            self._obs = env.state = g.carry
+        else:
+            g.replay()
+            self._obs = g.last_obs
         env._elapsed = steps - (cuts[-1] + 1) if cuts else start_elapsed + steps
         return self._build_marked_experience(steps, cuts, g.seg_returns)
 

@@ -31,6 +31,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "cartpole_rollout_kernels.hip"),
         os.path.join(HIP_DIR, "pendulum_rollout_kernels.hip"),
         os.path.join(HIP_DIR, "pendulum_collect_kernels.hip"),
+        os.path.join(HIP_DIR, "synthetic_collect_kernels.hip"),
         os.path.join(HIP_DIR, "eval_kernels.hip"),
         os.path.join(HIP_DIR, "update_kernels.hip"),
         os.path.join(HIP_DIR, "offpolicy_kernels.hip"),

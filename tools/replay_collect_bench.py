@@ -1,7 +1,9 @@
-"""Per-epoch `sample()` + `add_experience()` time of the Pendulum off-policy
-collection paths on one GPU.
+"""Per-epoch `sample()` + `add_experience()` time of the off-policy collection
+paths on one GPU, on Pendulum-v1 (the default) or a synthetic env.
 
     python tools/replay_collect_bench.py --out profiles/bench_replay_collect_1gpu.json
+    python tools/replay_collect_bench.py --env Ant-v4 \
+        --out profiles/bench_synthetic_collect_1gpu.json
 
 Actor [3,256,256,1] (ReLU, Tanh head; the benchmark actor), both behaviour
 policies of `OffPolicyAlgorithm.learn` (uniform warm-up, noised actor), at
@@ -21,6 +23,12 @@ lockstep cut pattern of horizon 200 to have its graph); then the paths run
 alternated for `--rounds` rounds in this one process, each timed window
 `--epochs` calls long with one synchronise before and one after, so the
 run-to-run spread is visible next to the ratios.
+
+With `--env` naming a synthetic env (Ant-v4, ...) the same protocol runs on
+VectorEnv(env) / DeviceVectorEnv(env) with the actor [O,256,256,A] and
+synthetic_collect_fused; a shape is then warmed for at least
+horizon / steps + 5 epochs, so that the 1000-step horizon's cut patterns
+have their graphs too.
 """
 import argparse
 import json
@@ -48,12 +56,31 @@ PATHS = {
 }
 
 
+def actor_dims(env_id):
+    if env_id == "Pendulum-v1":
+        return DIMS
+    from rl_replicas_amd.envs import MUJOCO_SHAPES
+
+    obs_dim, act_dim = MUJOCO_SHAPES[env_id]
+    return [obs_dim, 256, 256, act_dim]
+
+
+def warmup_epochs(env_id, warmup, steps):
+    """Epochs that bring every lockstep cut pattern of the env's horizon."""
+    if env_id == "Pendulum-v1":
+        return warmup
+    from rl_replicas_amd import envs
+
+    horizon = envs.make(env_id).spec.max_episode_steps or 0
+    return max(warmup, horizon // steps + 5)
+
+
 def paths_of(mode):
     # uniform mode reads no net: the persistent kernel has no wide regime
     return [p for p in PATHS if not (mode == "uniform" and p == "d_persistent_wg1024")]
 
 
-def make_runner(name, mode, n_envs, steps):
+def make_runner(name, mode, n_envs, steps, env_id="Pendulum-v1"):
     import torch.nn as nn
 
     from rl_replicas_amd import envs, ops
@@ -64,17 +91,24 @@ def make_runner(name, mode, n_envs, steps):
     from rl_replicas_amd.utils import add_noise_to_get_action
 
     torch.manual_seed(0)
-    net = MLP(DIMS, activation_function=nn.ReLU, output_activation_function=nn.Tanh).to("cuda")
+    pendulum = env_id == "Pendulum-v1"
+
+    def device_env():
+        if pendulum:
+            return envs.DevicePendulumEnv(n_envs, device="cuda")
+        return envs.DeviceVectorEnv(env_id, n_envs, device="cuda")
+
+    net = MLP(actor_dims(env_id), activation_function=nn.ReLU, output_activation_function=nn.Tanh).to("cuda")
     det = DeterministicPolicy(net, ops.make_adam(net.parameters(), lr=1e-3))
     buf = ReplayBuffer(RING, device="cuda")
     if PATHS[name] is None:
-        env = envs.VectorEnv("Pendulum-v1", num_envs=n_envs)
+        env = envs.VectorEnv(env_id, num_envs=n_envs)
         sampler = VectorSampler(env, seed=0, is_continuous=True)
     elif name == "e_device_eager":
-        env = envs.DevicePendulumEnv(n_envs, device="cuda")
+        env = device_env()
         sampler = DeviceSampler(env, seed=0, is_continuous=True)
     else:
-        env = envs.DevicePendulumEnv(n_envs, device="cuda")
+        env = device_env()
         sampler = DeviceReplaySampler(env, buf, seed=0)
     policy = (RandomPolicy(env.action_space) if mode == "uniform"
               else add_noise_to_get_action(det, env.action_space, 0.1))
@@ -114,6 +148,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=45)
     ap.add_argument("--epochs", type=int, default=100)
+    ap.add_argument("--env", default="Pendulum-v1",
+                    help="Pendulum-v1 or a synthetic env id (Ant-v4, ...)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -126,11 +162,12 @@ def main():
     for mode in MODES:
         for shape in SHAPES:
             for name in paths_of(mode):
-                run, check = make_runner(name, mode, *shape)
-                for _ in range(args.warmup):  # allocations, every graph pattern
+                run, check = make_runner(name, mode, *shape, env_id=args.env)
+                warm = warmup_epochs(args.env, args.warmup, shape[1])
+                for _ in range(warm):  # allocations, every graph pattern
                     run()
                 torch.cuda.synchronize()
-                check(args.warmup)
+                check(warm)
                 runners[(mode, shape, name)] = run
                 print(f"warmed {mode} {shape} {name}", file=sys.stderr, flush=True)
 
@@ -140,10 +177,14 @@ def main():
             samples[key].append(timed_window(run, args.epochs))
         print(f"round {r + 1}/{args.rounds} done", file=sys.stderr, flush=True)
 
-    result = {"device": torch.cuda.get_device_name(0), "actor": DIMS, "ring_slots": RING,
+    result = {"device": torch.cuda.get_device_name(0), "actor": actor_dims(args.env),
+              "ring_slots": RING,
               "rounds": args.rounds, "warmup_epochs": args.warmup,
               "timed_epochs": args.epochs, "what": "ms per sample() + add_experience()",
               "cases": []}
+    if args.env != "Pendulum-v1":
+        result = {"env": args.env, **result,
+                  "warmup_epochs_min_per_shape": "horizon / steps + 5"}
     for mode in MODES:
         for shape in SHAPES:
             per_path = {}
